@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Gauss-ILRMA (IP) iterations/s on synthetic spectrograms.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -13,15 +13,25 @@ off) over this rank's batch of utterances, inputs resident in HBM.  N=1 workload
 (M=4, F=1025, T=4096, K=4, one utterance); N>1 = the same per-GPU workload on every rank (independent utterances,
 no data-path collective: "weak" scaling); value = utterance-iterations/s over all ranks.
 
-Rank 0 prints ONE JSON line with
+A plain run does only what the headline needs: set-up, the pre-warm and the W warm-up steps, the K timed steps, the
+outputs (`--dump-outputs DIR`) and the result line, with `ms_per_step` = milliseconds per timed step.  The pre-warm
+runs from the model's initial state and the state is put back afterwards, so the timed steps always start from the
+same seeded state and their outputs are the same from run to run.  `--dump-outputs DIR` writes, after the timed steps,
+rank 0's model as update_once() left it -- demix_filter, basis, activation and a fixed, seeded sample of estimation
+(y = W x) -- as DIR/<name>.npy in the compute precision, complex values as a trailing (real, imag) axis.
+
+Everything else is measured only with `--full` (each leg can still be dropped with its own switch); the JSON line
+then also holds
   roofline      covariance-accumulate kernel alone, HIP events on the launch stream, one utterance (X = 268.7 MB,
                 within 0.1 % of the 256 MiB Infinity Cache) -- and `roofline_b8`, the same kernel on 8 utterances in
                 one launch (2.15 GB: nothing of X survives in the cache), the figure to quote for sustained HBM rate;
   cpu_baseline  (N=1) the NumPy oracle on the same workload timed on this host: streaming form (`value`) and the
                 reference's own materialising XX/R form on a quarter of the frames (`reference_form`);
-  config5       (N>1, or --config5) 64 seeded utterances block-partitioned over the ranks, one batched launch
-                sequence per rank, the reference's default 100 iterations + final projection back:
-                `value` without the edges, `value_incl_edges` with scatter X / gather Y over RCCL.
+  config5       (N>1, or --config5 on, which runs it also without --full) 64 seeded utterances block-partitioned over
+                the ranks, one batched launch sequence per rank, the reference's default 100 iterations + final
+                projection back: `value` without the edges, `value_incl_edges` with scatter X / gather Y over RCCL;
+and the side lines of the same workload (value_with_loss, value_f32, value_k10*, value_b8, other_configs).  In a plain
+run `roofline`, `roofline_b8` and `cpu_baseline` are null.
 """
 import argparse
 import gc
@@ -47,6 +57,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=500)
     p.add_argument("--warmup", type=int, default=50)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write rank 0's model as the last step left it to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beyond the headline: roofline, side lines, other configs, HBM traffic, CPU "
+                        "baseline, and config 5 when N > 1 (the --with-* / --cpu-iters / --roofline-b8 / "
+                        "--measure-traffic switches below select among them)")
     p.add_argument("--dtype", default="float64", choices=["float64", "float32"],
                    help="storage/compute type of the kernels; float64 = the reference's complex128 path")
     p.add_argument("--utterances-per-gpu", type=int, default=1)
@@ -83,7 +99,8 @@ def parse():
                         "tools/pmc_traffic.py: measure_case) -> roofline.traffic of THIS run; falls back to "
                         "profiles/cov_traffic.json when rocprofv3 is missing or fails (traffic_source says which)")
     p.add_argument("--config5", default="auto", choices=["auto", "on", "off"],
-                   help="config-5 leg (64 utterances sharded over the ranks); auto = only when N > 1")
+                   help="config-5 leg (64 utterances sharded over the ranks); auto = only with --full and N > 1, "
+                        "on = also without --full")
     p.add_argument("--config5-utterances", type=int, default=64)
     p.add_argument("--config5-iterations", type=int, default=100)
     p.add_argument("--config5-timeout", type=int, default=420, help="seconds before the config-5 leg is abandoned")
@@ -161,6 +178,30 @@ def time_cov_kernel(torch, eng, X, Td, Vd, reps):
     e1.record(stream)
     e1.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+DUMP_MAX_VALUES = 2 << 20  # real values per written array: 16 MB in float64, at most 64 MB over the four arrays
+
+
+def dump_outputs(torch, model, out_dir):
+    """What a caller of update_once() receives from the model after the last timed step: demix_filter, basis and
+    activation in full (or a seeded sample when one holds more than DUMP_MAX_VALUES real values) and a seeded sample of
+    estimation = W x (the whole of it is X's size: 268.7 MB at config 4).  A sample is taken over the flattened array
+    with a fixed seed, so the same arguments pick the same entries; written in the compute precision, complex values as
+    a trailing (real, imag) axis."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"demix_filter": model._Wd, "basis": model._Td, "activation": model._Vd,
+              "estimation": model._engine.demix(model._X, model._Wd)}
+    for name, t in arrays.items():
+        a = torch.view_as_real(t) if t.is_complex() else t
+        per_entry = 2 if t.is_complex() else 1
+        if t.numel() * per_entry > DUMP_MAX_VALUES:
+            n = DUMP_MAX_VALUES // per_entry
+            idx = np.sort(np.random.default_rng(12345).choice(t.numel(), size=n, replace=False))
+            a = a.reshape(t.numel(), *a.shape[t.dim():])[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+    torch.cuda.synchronize(model._engine.dev)
 
 
 def host_description():
@@ -414,9 +455,12 @@ def main():
         at least --prewarm-ms, then until two consecutive chunks take the same time within 1 % (at most 8 x --prewarm-ms).
         The part takes ~100 ms of load to settle as a rule, but a process that starts on a box that has just been idle -- what
         the driver's single run is -- was seen to need more: five runs of the driver's command in a row read 0.1875, 0.1805,
-        0.1814, 0.1790, 0.1788 ms per step with the fixed 150 ms (profiles/r06_bench_driver_cmd_fourth_box.json)."""
+        0.1814, 0.1790, 0.1788 ms per step with the fixed 150 ms (profiles/r06_bench_driver_cmd_fourth_box.json).
+        The number of pre-warm steps varies from run to run, so the model's state (demix_filter, basis, activation) is
+        copied back in place afterwards: the warm-up and timed steps start from the seeded state of make_model()."""
         if args.prewarm_ms <= 0:
             return
+        saved = [(t, t.clone()) for t in (model._Wd, model._Td, model._Vd)]
         t_start = time.perf_counter()
         t_min, t_max = t_start + args.prewarm_ms * 1e-3, t_start + 8 * args.prewarm_ms * 1e-3
         prev = None
@@ -430,6 +474,10 @@ def main():
             if now >= t_max or (now >= t_min and prev is not None and abs(dt - prev) <= 0.01 * prev):
                 break
             prev = dt
+        for t, t0 in saved:
+            t.copy_(t0)
+        model._touch("W", "T", "V")
+        del saved
         prewarm_spent[0] = max(prewarm_spent[0], (time.perf_counter() - t_start) * 1e3)
 
     def timed_steps(model, steps, warmup, with_loss=False):
@@ -466,7 +514,7 @@ def main():
     # stream.  Running them before the timed steps also brings the clocks up, so a short --steps run is not low.
     roofline = roofline_b8 = None
     r = 8 if args.dtype == "float64" else 4
-    if rank == 0:
+    if rank == 0 and args.full:
         eng = model._engine
         nbytes, kernel_name = cov_contract_bytes(B, M, F, T, K, r)
         ms = time_cov_kernel(torch, eng, model._X, model._Td, model._Vd, args.kernel_reps)
@@ -504,6 +552,8 @@ def main():
 
     elapsed = timed_steps(model, args.steps, args.warmup)
     model._check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, model, args.dump_outputs)
     total_units = n_gpus * B * args.steps  # utterance-iterations
     value = total_units / elapsed
 
@@ -511,21 +561,21 @@ def main():
     # side lines of the same workload (never `value`): the loss recorded (the reference's default), the float32 storage
     # mode, the reference's default n_basis, 8 utterances per launch
     side_steps, side_warm = min(args.steps, 100), min(args.warmup, 10)
-    if args.with_loss:
+    if args.full and args.with_loss:
         ml = make_model(True)
         extra["value_with_loss"] = round(n_gpus * B * side_steps / timed_steps(ml, side_steps, side_warm, with_loss=True), 2)
         del ml
-    if args.with_f32 and args.dtype == "float64":
+    if args.full and args.with_f32 and args.dtype == "float64":
         m32 = make_model(False, dtype="float32")
         extra["value_f32"] = round(n_gpus * B * side_steps / timed_steps(m32, side_steps, side_warm), 2)
         del m32
-    if args.with_default_basis and K != 10:
+    if args.full and args.with_default_basis and K != 10:
         for key, rl in (("value_k10", False), ("value_k10_with_loss", True)):
             mk = make_model(rl, n_basis=10)
             extra[key] = round(n_gpus * B * side_steps / timed_steps(mk, side_steps, side_warm, with_loss=rl), 2)
             extra[key + "_host_us_per_step"] = round(host_loop[0] * 1e6, 1)
             del mk
-    if args.with_b8 and B == 1 and (M, F, T) == (4, 1025, 4096):
+    if args.full and args.with_b8 and B == 1 and (M, F, T) == (4, 1025, 4096):
         B8 = 8
         X8 = synth_mixture(torch, dev, B8, M, F, T, seed=2000 + rank).to(cplx).contiguous()
         m8 = make_model(False, x=X8)
@@ -534,7 +584,7 @@ def main():
         extra["value_b8_note"] = "utterance-iterations/s, %d utterances per launch (config 5's per-GPU batch), %d steps" % (B8, s8)
         del m8, X8
     torch.cuda.empty_cache()
-    if args.with_other_configs and rank == 0 and args.dtype == "float64":
+    if args.full and args.with_other_configs and rank == 0 and args.dtype == "float64":
         extra["other_configs"] = other_configs_leg(torch, dev)
 
     # ---------------- HBM traffic of the roofline kernel, measured now (every timed leg is over: the child processes and
@@ -563,7 +613,7 @@ def main():
 
     # ---------------- CPU baseline: the NumPy oracle on the same workload (rank 0, N=1 only)
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and args.cpu_iters > 0:
+    if args.full and rank == 0 and n_gpus == 1 and args.cpu_iters > 0:
         cpu_baseline = cpu_baseline_leg(args, X[0].cpu().numpy(), M, F, T, K)
 
     out = None
@@ -575,6 +625,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "prewarm_ms": args.prewarm_ms,
             "prewarm_ms_spent_max": round(prewarm_spent[0], 1),
             "ms_per_step": round(1e3 * elapsed / args.steps, 4),
@@ -596,7 +647,7 @@ def main():
     # ---------------- config 5: sharded batch of utterances with and without the RCCL edges.  The headline
     # measurement above is complete at this point; a watchdog makes sure its line is printed even if a point-to-point
     # edge of this leg were to hang (rank 0 prints the line with config5.error, every rank leaves).
-    if args.config5 == "on" or (args.config5 == "auto" and n_gpus > 1):
+    if args.config5 == "on" or (args.config5 == "auto" and args.full and n_gpus > 1):
         import threading
 
         def give_up():

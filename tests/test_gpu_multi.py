@@ -119,7 +119,7 @@ def test_rccl_single_rank_group_and_bench_under_launcher():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "rccl ok" in r.stdout, r.stderr[-2000:]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--steps",
            "3", "--warmup", "1", "--bins", "129", "--frames", "512", "--cpu-iters", "0", "--kernel-reps", "3",
            "--roofline-b8", "2", "--config5", "on", "--config5-utterances", "3", "--config5-iterations", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -317,8 +317,8 @@ def test_bench_n_ranks_whole_flow_on_one_gpu(world, n_utt):
     from audio_source_separation_amd import distributed as D
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--comm-backend", "gloo", "--share-gpu",
-           "--steps", "3", "--warmup", "1", "--bins", "129", "--frames", "512", "--cpu-iters", "0", "--kernel-reps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--comm-backend", "gloo",
+           "--share-gpu", "--steps", "3", "--warmup", "1", "--bins", "129", "--frames", "512", "--cpu-iters", "0", "--kernel-reps", "3",
            "--roofline-b8", "2", "--config5-utterances", str(n_utt), "--config5-iterations", "2", "--prewarm-ms", "5"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -9,13 +9,13 @@ cd /tmp && export TMPDIR=/tmp
 py() { python "$@"; }
 B="$ROOT/bench.py"
 SIDE="--measure-traffic 0 --with-b8 0 --with-loss 0"
-py $B > $OUT/bench_f64.json 2> $OUT/bench_f64.err
+py $B --full > $OUT/bench_f64.json 2> $OUT/bench_f64.err
 ( cd $ROOT && bash tools/driver_cmd_runs.sh $TAG 5 > $OUT/bench_driver_cmd_summary.txt 2>&1 )   # the driver's exact command, 5 runs + the 500/50 line
-py $B --dtype float32 --cpu-iters 0 $SIDE > $OUT/bench_f32.json 2>/dev/null
-py $B --cpu-iters 0 --utterances-per-gpu 8 --steps 100 --warmup 10 --roofline-b8 0 $SIDE > $OUT/bench_f64_8utt.json 2>/dev/null
-py $B --cpu-iters 0 --basis 10 --steps 200 --warmup 20 --with-b8 0 --with-loss 0 > $OUT/bench_f64_k10.json 2>/dev/null
-py $B --cpu-iters 0 --basis 10 --utterances-per-gpu 8 --steps 50 --warmup 5 --roofline-b8 0 $SIDE > $OUT/bench_f64_k10_8utt.json 2>/dev/null
-py $B --cpu-iters 0 --config5 on --config5-utterances 64 --config5-iterations 100 --roofline-b8 0 $SIDE > $OUT/bench_f64_config5_1gpu_64utt.json 2>/dev/null
+py $B --full --dtype float32 --cpu-iters 0 $SIDE > $OUT/bench_f32.json 2>/dev/null
+py $B --full --cpu-iters 0 --utterances-per-gpu 8 --steps 100 --warmup 10 --roofline-b8 0 $SIDE > $OUT/bench_f64_8utt.json 2>/dev/null
+py $B --full --cpu-iters 0 --basis 10 --steps 200 --warmup 20 --with-b8 0 --with-loss 0 > $OUT/bench_f64_k10.json 2>/dev/null
+py $B --full --cpu-iters 0 --basis 10 --utterances-per-gpu 8 --steps 50 --warmup 5 --roofline-b8 0 $SIDE > $OUT/bench_f64_k10_8utt.json 2>/dev/null
+py $B --full --cpu-iters 0 --config5 on --config5-utterances 64 --config5-iterations 100 --roofline-b8 0 $SIDE > $OUT/bench_f64_config5_1gpu_64utt.json 2>/dev/null
 py $ROOT/tools/bench_configs.py > $OUT/bench_configs.json 2>/dev/null
 py $ROOT/tools/nmf_bench.py float64 > $OUT/nmf_bench_f64.txt 2>/dev/null
 py $ROOT/tools/nmf_bench.py float32 > $OUT/nmf_bench_f32.txt 2>/dev/null
@@ -26,10 +26,10 @@ for c in cfg1 cfg3; do for d in float64 float32; do py $ROOT/tools/probes/small_
 for d in float64 float32; do py $ROOT/tools/probes/call_cfgs.py $d 2>/dev/null >> $OUT/call_cfgs.txt; done
 # rocprofv3 kernel tables: the driver's own command line, the K=10 line, NMF config 2, the wide-channel path
 RP="--cpu-iters 0 --measure-traffic 0 --with-b8 0 --with-loss 0 --with-other-configs 0"
-rocprofv3 --kernel-trace --stats -d $OUT/prof_cfg4 -o p -- python $B --steps 20 --warmup 5 $RP --with-f32 0 --with-default-basis 0 > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $OUT/prof_cfg5_8utt -o p -- python $B --steps 20 --warmup 5 $RP --utterances-per-gpu 8 --roofline-b8 0 --with-f32 0 --with-default-basis 0 > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $OUT/prof_f32 -o p -- python $B --steps 20 --warmup 5 $RP --dtype float32 --roofline-b8 0 --with-default-basis 0 > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $OUT/prof_k10 -o p -- python $B --steps 20 --warmup 5 $RP --basis 10 --with-f32 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_cfg4 -o p -- python $B --full --steps 20 --warmup 5 $RP --with-f32 0 --with-default-basis 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_cfg5_8utt -o p -- python $B --full --steps 20 --warmup 5 $RP --utterances-per-gpu 8 --roofline-b8 0 --with-f32 0 --with-default-basis 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_f32 -o p -- python $B --full --steps 20 --warmup 5 $RP --dtype float32 --roofline-b8 0 --with-default-basis 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_k10 -o p -- python $B --full --steps 20 --warmup 5 $RP --basis 10 --with-f32 0 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d $OUT/prof_nmf -o p -- python $ROOT/tools/nmf_bench.py float64 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d $OUT/prof_m8 -o p -- python $ROOT/tools/widem_bench.py 8:4 > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d $OUT/prof_m5 -o p -- python $ROOT/tools/widem_bench.py 5:4 > /dev/null 2>&1

@@ -13,7 +13,7 @@ for i in $(seq 1 $N); do
   python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -n 1 >> $OUT/bench_driver_cmd.json
   [ -n "$OTHER" ] && python3 $OTHER --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -n 1 >> $OUT/bench_driver_cmd_other.json
 done
-python3 bench.py --cpu-iters 0 2>/dev/null | tail -n 1 > $OUT/bench_f64_500_50.json
+python3 bench.py --full --cpu-iters 0 2>/dev/null | tail -n 1 > $OUT/bench_f64_500_50.json
 python3 - "$OUT" <<'PY'
 import json, sys, os
 out = sys.argv[1]

@@ -8,7 +8,7 @@ cd $ROOT
 for rep in $(seq 1 $REPS); do
   for spec in "$@"; do
     name=${spec%%=*}; lib=${spec#*=}
-    ASSX_LIB_PATH=$ROOT/$lib python bench.py --cpu-iters 0 --with-f32 0 --with-default-basis 0 --with-other-configs 0 --with-loss ${AB_LOSS:-0} \
+    ASSX_LIB_PATH=$ROOT/$lib python bench.py --full --cpu-iters 0 --with-f32 0 --with-default-basis 0 --with-other-configs 0 --with-loss ${AB_LOSS:-0} \
       --with-b8 ${AB_B8:-0} --steps ${AB_STEPS:-300} --warmup 30 ${AB_ARGS:-} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -6,6 +6,6 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/${TAG:-xpol}; mkdir -p $O; C=audio_source_separation_amd/csrc
 for rep in 1 2; do for v in base nt sc1; do
   echo "== $v (rep $rep)" >> $O/x_policy_ab.txt
-  ASSX_LIB_PATH=$C/ab/libassx_$v.so python bench.py --cpu-iters 0 --roofline-b8 0 --with-f32 0 --with-default-basis 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg4', d['value'], 'it/s', d['ms_per_step'], 'ms; cov kernel', d['roofline']['kernel_ms'], 'ms')" >> $O/x_policy_ab.txt
+  ASSX_LIB_PATH=$C/ab/libassx_$v.so python bench.py --full --cpu-iters 0 --roofline-b8 0 --with-f32 0 --with-default-basis 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg4', d['value'], 'it/s', d['ms_per_step'], 'ms; cov kernel', d['roofline']['kernel_ms'], 'ms')" >> $O/x_policy_ab.txt
   ASSX_LIB_PATH=$C/ab/libassx_$v.so python tools/auxiva_bench.py 2>/dev/null | grep "M=4" >> $O/x_policy_ab.txt
 done; done
