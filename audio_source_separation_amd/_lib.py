@@ -62,6 +62,16 @@ SIGNATURES = {
     "assx_auxiva_spatial_update": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_idlma_space_update": (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_fastmnmf_update_diagonalizer": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "assx_fastmnmf_project": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_update_nmf": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_update_scm": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_update_diagonalizer_model": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _i, _i, _i, _i, _i, _i,
+                                                     _i, _vp]),
+    "assx_fastmnmf_normalize_power": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_separate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_fastmnmf_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
+                                   _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -1,15 +1,23 @@
-"""The diagonaliser update of FastMNMF on MI355X.
+"""FastMNMF on MI355X.
 
-`FastMultichannelISNMF.update_diagonalizer` (/root/reference/src/bss/mnmf.py:848-888) is a weighted covariance per
-CHANNEL m -- weights R[f,t,m] = sum_n Lambda[n,f,t] g[n,f,m] -- followed by the iterative-projection sweep with the
-normaliser floored at eps: the very kernels of the ILRMA spatial update.  The rest of FastMNMF (NMF and spatial
-covariance updates) is out of scope.
+`FastMultichannelISNMF` is the drop-in for the reference class of the same name (`src/bss/mnmf.py`:
+637-946): every step of its iteration -- the NMF update of basis and activation, the spatial-covariance update, the
+diagonaliser update and the 'power' normalisation -- and its loss and `separate` run as HIP kernels
+(csrc/assx_fastmnmf.hip); without callbacks the whole loop is one library call (assx_fastmnmf_iterate).  Its output
+is `separate(input)`, (n_sources, n_bins, n_frames): the sources' images at channel `reference_id`.
+
+`update_diagonalizer` (mnmf.py:848-888) is also offered as a free function for callers that keep their NMF model
+elsewhere: a weighted covariance per CHANNEL m -- weights R[f,t,m] = sum_n Lambda[n,f,t] g[n,f,m] -- followed by the
+iterative-projection sweep with the normaliser floored at eps, on the very kernels of the ILRMA spatial update.
 """
 import numpy as np
 
 from .._device import to_device, to_numpy, torch
+from .._loss import LazyLossList
+from .._state import DeviceArray, DeviceState
 from .. import _lib
 from ..algorithm.projection_back import _engine
+from ..ops import Engine
 
 EPS = 1e-12
 THRESHOLD = 1e+12
@@ -63,3 +71,330 @@ def update_diagonalizer(input, diagonalizer, spatial_covariance, variance=None, 
         return Q if batched else Q[0]
     Q = to_numpy(Q, np.complex128)
     return Q if batched else Q[0]
+
+
+class FastMultichannelISNMF(DeviceState):
+    """
+    Reference: "Fast Multichannel Source Separation Based on Jointly Diagonalizable Spatial Covariance Matrices"
+    (mnmf.py:637-946).  Supported: 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64.
+
+    `basis` (n_sources, n_bins, n_basis), `activation` (n_sources, n_basis, n_frames), `spatial_covariance`
+    (n_sources, n_bins, n_channels), `diagonalizer` (n_bins, n_channels, n_channels), `latent` and `estimation` live on
+    the device and read as NumPy arrays (an in-place edit reaches the next kernel).  A leading utterance axis on the
+    input, (B, n_channels, n_bins, n_frames), adds one to every attribute and to the output.  One utterance must stay
+    below 2^28 samples (n_channels * n_bins * n_frames).  Arrays that do not fit the input -- a `separate` input of
+    other sizes than the fitted model, a reassigned attribute of another shape -- raise ValueError.
+    """
+    basis = DeviceArray("W", complex_=False)
+    activation = DeviceArray("H", complex_=False)
+    spatial_covariance = DeviceArray("g", complex_=False)
+    diagonalizer = DeviceArray("Q", complex_=True)
+    latent = DeviceArray("Z", complex_=False)
+    estimation = DeviceArray("Y", complex_=True)
+
+    MAX_CHANNELS, MAX_SOURCES, MAX_BASIS = 8, 8, 64
+
+    def __init__(self, n_basis=10, n_sources=None, partitioning=False, normalize='power', reference_id=0, callbacks=None,
+                 recordable_loss=True, eps=EPS, threshold=THRESHOLD, *, dtype='float64', device=None):
+        if callbacks is not None:
+            if callable(callbacks):
+                callbacks = [callbacks]
+            self.callbacks = callbacks
+        else:
+            self.callbacks = None
+
+        self.eps = eps
+        self.n_basis = n_basis
+        self.n_sources = n_sources
+
+        self.input = None
+        self.recordable_loss = recordable_loss
+        if self.recordable_loss:
+            self.loss = LazyLossList()  # a list; entries are materialised from HBM on first read
+        else:
+            self.loss = None
+
+        self.partitioning = partitioning
+        self.normalize = normalize
+        self.reference_id = reference_id
+
+        self.threshold = threshold
+
+        self.dtype = dtype
+        self.device = device
+        self._engine = None
+        self._ws = None
+        self._ws_key = None
+        self._xt_src = None
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            self._engine = Engine(dtype=self.dtype, device=self.device)
+        return self._engine
+
+    def _reset(self, **kwargs):
+        """mnmf.py:47-61, 653-689: Q and g are reset on every call; basis / activation (and latent) only when absent."""
+        assert self.input is not None, "Specify data!"
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+        eng = self._ensure_engine()
+        X = self.input
+        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
+        if ndim not in (3, 4):
+            raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
+        shape = tuple(int(d) for d in (X.shape if isinstance(X, torch.Tensor) else np.shape(X)))
+        B, n_channels, n_bins, n_frames = (1,) * (4 - ndim) + shape
+
+        n_sources = self.n_sources
+        if n_sources is None:
+            n_sources = n_channels
+        self.n_sources, self.n_channels = n_sources, n_channels
+        self.n_bins, self.n_frames = n_bins, n_frames
+        n_basis = self.n_basis
+        # the limits are checked before the input is uploaded
+        if not (2 <= n_channels <= self.MAX_CHANNELS and 1 <= n_sources <= self.MAX_SOURCES
+                and 1 <= n_basis <= self.MAX_BASIS):
+            raise ValueError("FastMultichannelISNMF supports 2 <= n_channels <= {}, 1 <= n_sources <= {} and "
+                             "1 <= n_basis <= {}; got n_channels={}, n_sources={}, n_basis={}".format(
+                                 self.MAX_CHANNELS, self.MAX_SOURCES, self.MAX_BASIS, n_channels, n_sources, n_basis))
+        if n_channels * n_bins * n_frames >= 1 << 28:
+            raise ValueError("FastMultichannelISNMF: one utterance must stay below 2^28 samples (n_channels * n_bins * "
+                             "n_frames < 268435456: 4 GiB in complex128); got {} x {} x {}".format(
+                                 n_channels, n_bins, n_frames))
+
+        self._batched = ndim == 4
+        Xd = to_device(X, eng.prec.cplx, eng.dev)
+        if not self._batched:
+            Xd = Xd.unsqueeze(0)
+        self._X = Xd.contiguous()
+
+        Q = torch.eye(n_channels, dtype=eng.prec.cplx, device=eng.dev).repeat(B, n_bins, 1, 1)
+        G = np.ones((n_sources, n_bins, n_channels)) * 1e-2
+        for m in range(n_channels):
+            G[m % n_sources, :, m] = 1
+        G = to_device(G, eng.prec.real, eng.dev).unsqueeze(0).repeat(B, 1, 1, 1)
+
+        lead = (B,) if self._batched else ()
+        if self.partitioning:
+            if not hasattr(self, 'latent'):
+                self.latent = np.ones(lead + (n_sources, n_basis), dtype=np.float64) / n_sources
+            if not hasattr(self, 'basis'):
+                self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
+            if not hasattr(self, 'activation'):
+                self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
+            shapes = {"Z": (B, n_sources, n_basis), "W": (B, n_bins, n_basis), "H": (B, n_basis, n_frames)}
+        else:
+            if not hasattr(self, 'basis'):
+                self.basis = np.random.rand(*(lead + (n_sources, n_bins, n_basis)))
+            if not hasattr(self, 'activation'):
+                self.activation = np.random.rand(*(lead + (n_sources, n_basis, n_frames)))
+            shapes = {"W": (B, n_sources, n_bins, n_basis), "H": (B, n_sources, n_basis, n_frames)}
+        # the kernels take pointers and sizes: a warm-start array of another shape would be read past its end
+        names = {"Z": "latent", "W": "basis", "H": "activation"}
+        for name, shape in shapes.items():
+            got = tuple(self._dev(name, False).shape)
+            if got != shape:
+                raise ValueError("{}: expected shape {}, got {}".format(names[name], shape[0 if self._batched else 1:],
+                                                                     got[0 if self._batched else 1:]))
+        self._set_dev("Q", Q.contiguous())
+        self._set_dev("g", G.contiguous())
+
+        key = (B, n_channels, n_sources, n_bins, n_frames, n_basis, eng.prec.name)
+        if self._ws_key != key:
+            self._ws = eng.fastmnmf_workspace(*key[:6])
+            self._ws_key = key
+        self._xt_src = None
+        self._status = eng.new_status(B)
+
+    # ---- device views of the model ---------------------------------------------------------------------------------
+    def _model(self):
+        """(W, H, g, Q) as the kernels read them: with a partitioning function, Lambda = (Z W) H expanded per source."""
+        W, H = self._dev("W", False), self._dev("H", False)
+        if self.partitioning:
+            eng = self._engine
+            Z = self._dev("Z", False)
+            if Z.dim() != 3 or W.dim() != 3 or H.dim() != 3:
+                raise ValueError("partitioning: expected latent (n_sources, n_basis), basis (n_bins, n_basis) and "
+                                 "activation (n_basis, n_frames)")
+            B, N, K = (int(s) for s in Z.shape)
+            F, T = int(W.shape[1]), int(H.shape[2])
+            if tuple(W.shape) != (B, F, K) or tuple(H.shape) != (B, K, T):
+                raise ValueError("partitioning: latent {}, basis {} and activation {} do not fit together".format(
+                    tuple(Z.shape), tuple(W.shape), tuple(H.shape)))
+            Weff, Heff = eng.empty((B, N, F, K)), eng.empty((B, N, K, T))
+            eng.ilrma_expand_partitioned(Z, W, H, Weff, Heff)
+            W, H = Weff, Heff
+        return W, H, self._dev("g", False), self._dev("Q", True)
+
+    def _ensure_xt(self):
+        """x~ = |Q x|^2 of the current diagonaliser in the model's workspace (P1 of DESIGN.md section 9)."""
+        Q = self._dev("Q", True)
+        if self._xt_src is not Q:
+            W, H, g, _ = self._model()
+            self._engine.fastmnmf_project(self._X, Q, W, H, g, self._ws, eps=self.eps)
+            self._xt_src = Q
+
+    def _loss_dev(self):
+        W, H, g, Q = self._model()
+        loss = self._engine.empty((int(self._X.shape[0]),), dtype=torch.float64)
+        self._engine.fastmnmf_project(self._X, Q, W, H, g, self._ws, eps=self.eps, loss=loss)
+        self._xt_src = Q
+        return loss
+
+    def _record_loss(self):
+        loss = self._loss_dev()
+        if isinstance(self.loss, LazyLossList):
+            self.loss.append_device(loss, self._batched)
+        else:
+            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+
+    def _check_status(self):
+        if int(self._status.max().item()) & _lib.STATUS_SINGULAR:
+            self._status.zero_()
+            raise np.linalg.LinAlgError("Singular matrix")
+
+    # ---- the loop ----------------------------------------------------------------------------------------------------
+    def __call__(self, input, iteration=100, **kwargs):
+        """
+        Args:
+            input (n_channels, n_bins, n_frames)
+        Returns:
+            output (n_sources, n_bins, n_frames)
+        """
+        self.input = input
+
+        self._reset(**kwargs)
+
+        if iteration > 0 and self._fast_loop_ok():
+            # nothing observes the model between iterations: the loop is ONE call into the library
+            # (assx_fastmnmf_iterate enqueues the same entry points in the same order: bit-identical to the loop below)
+            self._run_fast_loop(iteration)
+        else:
+            if self.recordable_loss:
+                self._record_loss()
+
+            for idx in range(iteration):
+                self.update_once()
+
+                if self.recordable_loss:
+                    self._record_loss()
+
+                if self.callbacks is not None:
+                    self._check_status()
+                    self._set_dev("Y", self._separate_dev(self._X))
+                    for callback in self.callbacks:
+                        callback(self)
+        self._check_status()
+
+        Y = self._separate_dev(self._X)
+        self._set_dev("Y", Y)
+        if isinstance(input, torch.Tensor):
+            return Y if self._batched else Y[0]
+        return self.estimation
+
+    _OWN_STEPS = ("update_once", "update_NMF", "update_SCM", "update_diagonalizer", "compute_negative_loglikelihood",
+                  "_record_loss")
+
+    def _fast_loop_ok(self):
+        if self.callbacks is not None or self.partitioning or self.normalize not in (False, None, 0, '', 'power'):
+            return False
+        if any(getattr(type(self), name) is not getattr(FastMultichannelISNMF, name) for name in self._OWN_STEPS):
+            return False
+        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
+
+    def _run_fast_loop(self, iteration):
+        eng = self._engine
+        B = int(self._X.shape[0])
+        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
+        W, H, g, Q = self._model()
+        eng.fastmnmf_iterate(iteration, self._X, Q, W, H, g, self._ws, normalize=bool(self.normalize), eps=self.eps,
+                             threshold=self.threshold, status=self._status, loss=loss)
+        self._touch("W", "H", "g", "Q")
+        self._xt_src = Q if loss is not None else None  # the last projection ran only to record the last loss
+        if loss is not None:
+            self.loss.append_device_block(loss, self._batched)
+
+    def __repr__(self):
+        s = "FastMNMF("
+        s += "n_basis={n_basis}"
+        if hasattr(self, 'n_sources'):
+            s += ", n_sources={n_sources}"
+        if hasattr(self, 'n_channels'):
+            s += ", n_channels={n_channels}"
+        s += ", partitioning={partitioning}"
+        s += ", normalize={normalize}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def update_once(self):
+        """mnmf.py:737-773"""
+        self.update_NMF()
+        self.update_SCM()
+        self.update_diagonalizer()
+        if self.normalize:
+            if self.normalize == 'power':
+                if self.partitioning:
+                    raise ValueError("Not support partitioning function.")
+                W, H, g, Q = self._model()
+                self._engine.fastmnmf_normalize_power(self._X, Q, W, H, g, eps=self.eps)
+                self._touch("W", "H", "g", "Q")
+                self._xt_src = None
+            else:
+                raise ValueError("Not support normalization based on {}. Choose 'power'".format(self.normalize))
+
+    def update_NMF(self):
+        """mnmf.py:775-815: basis half, then the activation half with the new basis."""
+        if self.partitioning:
+            raise ValueError("Not support partitioning function.")
+        self._ensure_xt()
+        W, H, g, _ = self._model()
+        self._engine.fastmnmf_update_nmf(self._X, W, H, g, self._ws, eps=self.eps)
+        self._touch("W", "H")
+
+    def update_SCM(self):
+        """mnmf.py:817-846"""
+        if self.partitioning:
+            raise ValueError("Not support partitioning function.")
+        self._ensure_xt()
+        W, H, g, _ = self._model()
+        self._engine.fastmnmf_update_scm(self._X, W, H, g, self._ws, eps=self.eps)
+        self._touch("g")
+
+    def update_diagonalizer(self):
+        """mnmf.py:848-888, with R formed from the model on the fly."""
+        W, H, g, Q = self._model()
+        self._engine.fastmnmf_update_diagonalizer_model(self._X, Q, W, H, g, self._ws, eps=self.eps,
+                                                        threshold=self.threshold, status=self._status)
+        self._touch("Q")
+        self._xt_src = None
+
+    def compute_negative_loglikelihood(self):
+        """mnmf.py:890-917.  Syncs to return a Python float (an array of B with a batch axis)."""
+        loss = self._loss_dev()
+        if self._batched:
+            return to_numpy(loss, np.float64)
+        return np.float64(loss.item())
+
+    def _separate_dev(self, X):
+        W, H, g, Q = self._model()
+        status = self._engine.new_status(int(X.shape[0]))
+        Y = self._engine.fastmnmf_separate(X, Q, W, H, g, ref=self.reference_id, eps=self.eps, status=status)
+        if int(status.max().item()) & _lib.STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return Y
+
+    def separate(self, input):
+        """mnmf.py:919-946: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
+        eng = self._ensure_engine()
+        X = to_device(input, eng.prec.cplx, eng.dev)
+        batched = X.dim() == 4
+        if not batched:
+            X = X.unsqueeze(0)
+        Y = self._separate_dev(X.contiguous())
+        if isinstance(input, torch.Tensor):
+            return Y if batched else Y[0]
+        Y = to_numpy(Y, np.complex128)
+        return Y if batched else Y[0]

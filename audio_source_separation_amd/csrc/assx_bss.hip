@@ -2146,6 +2146,27 @@ int assx_fastmnmf_update_diagonalizer(assx_ctx* ctx, const void* X, void* Q, con
   });
 }
 
+}  // extern "C"
+
+namespace assx {
+// The tail of assx_fastmnmf_update_diagonalizer on weights R (B,M,F,T) that the caller has already formed: the
+// FastMNMF iteration (csrc/assx_fastmnmf.hip) builds R from basis, activation and spatial_covariance directly.
+int fastmnmf_weighted_ip(assx_ctx* ctx, const void* X, const void* Rw, void* Q, double eps, double threshold,
+                         int32_t* status, void* ws, int B, int M, int F, int T, int dtype, hipStream_t st) {
+  if (widem::handles(M)) return widem::weighted_ip(ctx, X, Rw, eps, threshold, eps, Q, status, ws, B, M, F, T, dtype, st);
+  return dispatch_rm(ctx, dtype, M, [&](auto rt, auto mt) -> int {
+    using R = decltype(rt);
+    constexpr int MM = decltype(mt)::value;
+    FlatPart fp;
+    int rc = run_cov_partial<R, MM>(ctx, WK_NFT, X, Rw, nullptr, nullptr, 1, 2.0, eps, ws, B, F, T, st, &fp);
+    if (rc) return rc;
+    return run_ip<R, MM>(ctx, nullptr, ws, fp, T, Q, nullptr, nullptr, threshold, status, B, F, st, eps);
+  });
+}
+}  // namespace assx
+
+extern "C" {
+
 int assx_auxiva_weights(assx_ctx* ctx, const void* X, const void* W, int kind, double eps, void* r, double* loss,
                         void* ws, int B, int M, int F, int T, int dtype, void* stream) {
   CHECK_COMMON(ctx, B, M, F, T);

@@ -81,4 +81,9 @@ int stack_gram_solve(assx_ctx* ctx, const void* A, size_t a_batch_stride, int na
                      size_t ob, size_t of, size_t oi, size_t oj, int32_t* status, int B, int F, int T, int dtype,
                      hipStream_t st);
 
+// V_m = mean_t x x^H / max(Rw[m], eps) and the eps-floored IP sweep over the channels of Q: the second half of
+// assx_fastmnmf_update_diagonalizer on caller-formed weights Rw (B,M,F,T).  Defined in assx_bss.hip.
+int fastmnmf_weighted_ip(assx_ctx* ctx, const void* X, const void* Rw, void* Q, double eps, double threshold,
+                         int32_t* status, void* ws, int B, int M, int F, int T, int dtype, hipStream_t st);
+
 }  // namespace assx

@@ -370,6 +370,102 @@ class Engine:
                     "assx_fastmnmf_update_diagonalizer")
         return Q
 
+    # ------------------------------------------------------------------ FastMNMF (bss/mnmf.py)
+    def _fastmnmf_dims(self, X, W, H, g, Q=None, ws=None):
+        """Sizes of a FastMNMF call, with every array checked against them: the kernels take pointers and sizes, so an
+        array of another shape (a separate() input longer than the fitted activation, a batched input on an unbatched
+        model, a reassigned attribute) would be read past its end.  Refused here with ValueError, before any launch."""
+        if X.dim() != 4 or W.dim() != 4:
+            raise ValueError("FastMNMF: expected X (B,M,F,T) and basis (B,N,F,K), got %s and %s"
+                             % (tuple(X.shape), tuple(W.shape)))
+        B, M, F, T = (int(d) for d in X.shape)
+        N, K = int(W.shape[1]), int(W.shape[3])
+        want = {"basis": (W, (B, N, F, K)), "activation": (H, (B, N, K, T)), "spatial_covariance": (g, (B, N, F, M))}
+        if Q is not None:
+            want["diagonalizer"] = (Q, (B, F, M, M))
+        want["input"] = (X, (B, M, F, T))
+        for name, (a, shape) in want.items():
+            dt = self.prec.cplx if name in ("input", "diagonalizer") else self.prec.real
+            if a.dtype != dt or a.device != self.dev:
+                raise ValueError("FastMNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
+            if tuple(a.shape) != shape:
+                raise ValueError("FastMNMF: %s has shape %s, but the input %s needs %s"
+                                 % (name, tuple(a.shape), (B, M, F, T), shape))
+        if ws is not None:
+            need = self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code)
+            if need == 0 or ws.numel() < need:
+                raise ValueError("FastMNMF: workspace of %d bytes, %d needed for B=%d M=%d N=%d F=%d T=%d K=%d"
+                                 % (ws.numel(), need, B, M, N, F, T, K))
+        return B, M, N, F, T, K
+
+    @staticmethod
+    def _fastmnmf_need(t, n, what):
+        if t is not None and (t.numel() < n or not t.is_contiguous()):
+            raise ValueError("FastMNMF: %s needs %d contiguous elements, got %s" % (what, n, tuple(t.shape)))
+
+    def fastmnmf_workspace(self, B, M, N, F, T, K):
+        """A model's own scratch: it carries x~ from assx_fastmnmf_project to the NMF and SCM updates."""
+        n = self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code)
+        if n == 0:
+            raise ValueError("FastMNMF supports 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; got "
+                             "n_channels=%d, n_sources=%d, n_basis=%d" % (M, N, K))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def fastmnmf_project(self, X, Q, W, H, g, ws, eps=1e-12, loss=None):
+        """x~ = |Q x|^2 into ws; loss (B,) float64 (or None) = the negative log-likelihood of the model as it stands."""
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
+        self._fastmnmf_need(loss, B, "loss")
+        self._check(self._L.assx_fastmnmf_project(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g), float(eps), ptr(loss),
+                                                  ptr(ws), B, M, N, F, T, K, self.prec.code, self._st()),
+                    "assx_fastmnmf_project")
+        return loss
+
+    def fastmnmf_update_nmf(self, X, W, H, g, ws, eps=1e-12):
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, None, ws)
+        self._check(self._L.assx_fastmnmf_update_nmf(self.ctx, ptr(W), ptr(H), ptr(g), float(eps), ptr(ws), B, M, N, F, T,
+                                                     K, self.prec.code, self._st()), "assx_fastmnmf_update_nmf")
+
+    def fastmnmf_update_scm(self, X, W, H, g, ws, eps=1e-12):
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, None, ws)
+        self._check(self._L.assx_fastmnmf_update_scm(self.ctx, ptr(W), ptr(H), ptr(g), float(eps), ptr(ws), B, M, N, F, T,
+                                                     K, self.prec.code, self._st()), "assx_fastmnmf_update_scm")
+
+    def fastmnmf_update_diagonalizer_model(self, X, Q, W, H, g, ws, eps=1e-12, threshold=1e12, status=None):
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
+        self._fastmnmf_need(status, B, "status")
+        self._check(self._L.assx_fastmnmf_update_diagonalizer_model(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g),
+                                                                    float(eps), float(threshold), ptr(status), ptr(ws), B,
+                                                                    M, N, F, T, K, self.prec.code, self._st()),
+                    "assx_fastmnmf_update_diagonalizer_model")
+
+    def fastmnmf_normalize_power(self, X, Q, W, H, g, eps=1e-12):
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q)
+        self._check(self._L.assx_fastmnmf_normalize_power(self.ctx, ptr(Q), ptr(W), ptr(H), ptr(g), float(eps), B, M, N, F,
+                                                          T, K, self.prec.code, self._st()),
+                    "assx_fastmnmf_normalize_power")
+
+    def fastmnmf_separate(self, X, Q, W, H, g, ref=0, eps=1e-12, status=None, out=None):
+        """(B,N,F,T) complex: x_hat[:, ref] of the reference's separate."""
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q)
+        self._fastmnmf_need(status, B, "status")
+        Y = out if out is not None else self.empty((B, N, F, T), complex_=True)
+        self._fastmnmf_need(Y, B * N * F * T, "out")
+        self._check(self._L.assx_fastmnmf_separate(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g), int(ref), float(eps),
+                                                   ptr(Y), ptr(status), B, M, N, F, T, K, self.prec.code, self._st()),
+                    "assx_fastmnmf_separate")
+        return Y
+
+    def fastmnmf_iterate(self, n_iter, X, Q, W, H, g, ws, normalize=True, eps=1e-12, threshold=1e12, status=None,
+                         loss=None):
+        """loss: (n_iter + 1, B) float64 or None."""
+        B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
+        self._fastmnmf_need(loss, (int(n_iter) + 1) * B, "loss")
+        self._fastmnmf_need(status, B, "status")
+        self._check(self._L.assx_fastmnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Q), ptr(W),
+                                                  ptr(H), ptr(g), float(eps), float(threshold), ptr(loss), ptr(status),
+                                                  ptr(ws), B, M, N, F, T, K, self.prec.code, self._st()),
+                    "assx_fastmnmf_iterate")
+
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):
         B, M, F, T = self._dims(X)

@@ -282,6 +282,49 @@ int assx_fastmnmf_update_diagonalizer(assx_ctx* ctx, const void* X, void* Q, con
                                       double eps, double threshold, void* R_scratch, int32_t* status, void* ws,
                                       int B, int M, int N, int F, int T, int dtype, void* stream);
 
+/* ---- (f5) FastMultichannelISNMF, the whole model (src/bss/mnmf.py:637-946) ------------------------------------------
+ * State: X (B,M,F,T) complex, Q (B,F,M,M) complex = diagonalizer, W (B,N,F,K) real = basis, H (B,N,K,T) real =
+ * activation, g (B,N,F,M) real = spatial_covariance.  x~[f,t,m] = |(Q x)[m]|^2, Lambda_n = W_n H_n, R[f,t,m] =
+ * sum_n Lambda_n g[n,f,m] (recomputed wherever it is needed, never stored by the model).  2 <= M <= 8, 1 <= N <= 8,
+ * 1 <= n_basis K <= 64 (ASSX_E_UNSUPPORTED outside).  `ws` holds x~ between calls: assx_fastmnmf_project writes it, the
+ * NMF and SCM updates read it, so the same `ws` (assx_fastmnmf_workspace_bytes) serves one model's calls in order.
+ *   assx_fastmnmf_project             x~ of the current Q into ws (mnmf.py:785-786, 825-826); with loss != NULL also
+ *                                     compute_negative_loglikelihood (mnmf.py:890-917) into loss (B,) float64:
+ *                                     sum (x~ + eps) / (R + eps) + log(R + eps) - T sum_f log|det(Q Q^T)|.
+ *   assx_fastmnmf_update_nmf          update_NMF (mnmf.py:775-815): basis half (reduce over t), then the activation half
+ *                                     (reduce over f) with the new basis; R floored at eps, denominators floored at eps.
+ *   assx_fastmnmf_update_scm          update_SCM (mnmf.py:817-846).
+ *   assx_fastmnmf_update_diagonalizer_model
+ *                                     update_diagonalizer (mnmf.py:848-888) with R formed from W, H, g; the same
+ *                                     covariance + eps-floored IP sweep as assx_fastmnmf_update_diagonalizer.
+ *   assx_fastmnmf_normalize_power     normalize == 'power' (mnmf.py:748-769): Q /= sqrt(max(mean_i sum_j |Q_ij|^2, eps)),
+ *                                     g rescaled and normalised over m, W absorbs the sums, W normalised over f, H absorbs.
+ *   assx_fastmnmf_separate            separate (mnmf.py:919-946): Y (B,N,F,T) complex = x_hat[:, ref] with R floored at
+ *                                     eps; an exactly singular Q sets ASSX_STATUS_SINGULAR (numpy.linalg.inv raises).
+ *   assx_fastmnmf_iterate             n_iter x { update_nmf ; update_scm ; update_diagonalizer_model ; normalize_power if
+ *                                     normalize == 1 } with the projections in between: the loop of __call__
+ *                                     (mnmf.py:691-722) without callbacks.  loss: (n_iter + 1, B) float64 or NULL;
+ *                                     entry i is the loss after i iterations. */
+size_t assx_fastmnmf_workspace_bytes(int B, int M, int N, int F, int T, int K, int dtype);
+int assx_fastmnmf_project(assx_ctx* ctx, const void* X, const void* Q, const void* W, const void* H, const void* g,
+                          double eps, double* loss, void* ws, int B, int M, int N, int F, int T, int K, int dtype,
+                          void* stream);
+int assx_fastmnmf_update_nmf(assx_ctx* ctx, void* W, void* H, const void* g, double eps, void* ws,
+                             int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+int assx_fastmnmf_update_scm(assx_ctx* ctx, const void* W, const void* H, void* g, double eps, void* ws,
+                             int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+int assx_fastmnmf_update_diagonalizer_model(assx_ctx* ctx, const void* X, void* Q, const void* W, const void* H,
+                                            const void* g, double eps, double threshold, int32_t* status, void* ws,
+                                            int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+int assx_fastmnmf_normalize_power(assx_ctx* ctx, void* Q, void* W, void* H, void* g, double eps,
+                                  int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+int assx_fastmnmf_separate(assx_ctx* ctx, const void* X, const void* Q, const void* W, const void* H, const void* g,
+                           int ref, double eps, void* Y, int32_t* status,
+                           int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+int assx_fastmnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* X, void* Q, void* W, void* H, void* g,
+                          double eps, double threshold, double* loss, int32_t* status, void* ws,
+                          int B, int M, int N, int F, int T, int K, int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */

@@ -1,0 +1,305 @@
+"""FastMultichannelISNMF on the GPU: the class against the reference's recorded output (tests/golden/fastmnmf) and the
+NumPy restatement (tests/fastmnmf_np.py), the reference's semantics, and the determinism of the HIP path."""
+import glob
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import fastmnmf_np as fm  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(HERE, "golden", "fastmnmf")
+NAMES = [os.path.basename(f)[:-4] for f in sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))]
+ATTRS = ("basis", "activation", "spatial_covariance", "diagonalizer")
+
+
+def rel(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
+
+
+def load(name):
+    return np.load(os.path.join(GOLDEN, name + ".npz"))
+
+
+def cls():
+    from audio_source_separation_amd.bss.mnmf import FastMultichannelISNMF
+    return FastMultichannelISNMF
+
+
+def normalize_of(g):
+    return str(g["normalize"]) or False
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_class_matches_reference(name):
+    g = load(name)
+    K = g["W0"].shape[2]
+    N = g["W0"].shape[0]
+    snaps = {}
+
+    def record(model):
+        it = len(model.loss) - 1
+        if it in (1, 2, 5, 20):
+            snaps[it] = {a: np.array(getattr(model, a)) for a in ATTRS + ("estimation",)}
+
+    np.random.seed(int(g["seed"]))
+    model = cls()(n_basis=K, n_sources=N, normalize=normalize_of(g), callbacks=record)
+    Y = model(g["X"], iteration=20)
+    assert Y.shape == g["output"].shape and Y.dtype == np.complex128
+    loss = np.asarray(model.loss)
+    assert np.max(np.abs(loss - g["loss"])) / np.max(np.abs(g["loss"])) < 1e-9
+    for it in (1, 2, 5, 20):
+        tol = 1e-9 if it <= 5 else 1e-6
+        for a in ATTRS:
+            assert rel(snaps[it][a], g["%s_%d" % (a, it)]) < tol, (it, a)
+        if it < 20:
+            assert rel(snaps[it]["estimation"], g["estimation_%d" % it]) < 1e-9, it
+    assert rel(Y, g["output"]) < 1e-6
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_fast_loop_matches_reference(name):
+    g = load(name)
+    np.random.seed(int(g["seed"]))
+    model = cls()(n_basis=g["W0"].shape[2], n_sources=g["W0"].shape[0], normalize=normalize_of(g))
+    Y = model(g["X"], iteration=20)
+    assert np.max(np.abs(np.asarray(model.loss) - g["loss"])) / np.max(np.abs(g["loss"])) < 1e-9
+    assert rel(model.basis, g["basis_20"]) < 1e-6
+    assert rel(Y, g["output"]) < 1e-6
+
+
+def test_float32_loss_curve():
+    g = load("fastmnmf_m4_n4_k10")
+    np.random.seed(int(g["seed"]))
+    model = cls()(n_basis=10, dtype="float32")
+    model(g["X"], iteration=20)
+    loss = np.asarray(model.loss)
+    assert np.max(np.abs(loss - g["loss"]) / np.abs(g["loss"])) < 1e-4
+
+
+def _small(M=3, N=2, K=4, F=17, T=96, seed=5):
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((M, F, T)) + 1j * rng.standard_normal((M, F, T))
+    W0, H0 = rng.random((N, F, K)), rng.random((N, K, T))
+    return X, W0, H0
+
+
+def test_no_callback_before_loop_and_estimation_in_loop():
+    X, W0, H0 = _small()
+    seen = []
+
+    def cb(model):
+        seen.append((len(model.loss), np.array(model.estimation)))
+
+    model = cls()(n_basis=4, n_sources=2, callbacks=cb)
+    model.basis, model.activation = W0.copy(), H0.copy()
+    model(X, iteration=3)
+    assert [s[0] for s in seen] == [2, 3, 4]
+    ref = fm.run(X, W0, H0, 1)[2]
+    est1 = fm.separate(X, ref["basis"], ref["activation"], ref["spatial_covariance"], ref["diagonalizer"])
+    assert rel(seen[0][1], est1) < 1e-9
+
+
+def test_rng_draws_basis_then_activation():
+    X, _, _ = _small()
+    np.random.seed(3)
+    W0, H0 = np.random.rand(2, 17, 4), np.random.rand(2, 4, 96)
+    np.random.seed(3)
+    model = cls()(n_basis=4, n_sources=2)
+    model(X, iteration=0)
+    assert np.array_equal(model.basis, W0) and np.array_equal(model.activation, H0)
+
+
+def test_warm_start_keeps_basis_resets_q_and_g():
+    X, W0, H0 = _small()
+    model = cls()(n_basis=4, n_sources=2)
+    model.basis, model.activation = W0.copy(), H0.copy()
+    model(X, iteration=2)
+    W1, H1 = np.array(model.basis), np.array(model.activation)
+    model(X, iteration=0)
+    assert np.array_equal(model.basis, W1) and np.array_equal(model.activation, H1)
+    Q0, g0 = fm.initial_state(3, 2, 17)
+    assert np.array_equal(model.diagonalizer, Q0) and np.array_equal(model.spatial_covariance, g0)
+    # the second call continues from the kept W, H with fresh Q, g: the restatement says the same
+    model(X, iteration=1)
+    _, losses, st = fm.run(X, W1, H1, 1)
+    assert rel(model.basis, st["basis"]) < 1e-9
+    assert abs(model.loss[-1] - losses[-1]) / abs(losses[-1]) < 1e-9
+
+
+def test_partitioning():
+    X, _, _ = _small()
+    np.random.seed(11)
+    model = cls()(n_basis=4, n_sources=2, partitioning=True)
+    Y = model(X, iteration=0)
+    Z, W, H = np.array(model.latent), np.array(model.basis), np.array(model.activation)
+    assert Z.shape == (2, 4) and W.shape == (17, 4) and H.shape == (4, 96)
+    We, He = fm.expand_partitioned(Z, W, H)
+    Q, g = fm.initial_state(3, 2, 17)
+    assert abs(model.loss[0] - fm.loss(X, We, He, g, Q)) / abs(model.loss[0]) < 1e-9
+    assert rel(Y, fm.separate(X, We, He, g, Q)) < 1e-9
+    with pytest.raises(ValueError, match="Not support partitioning function."):
+        model(X, iteration=1)
+
+
+def test_unknown_normalization_raises_after_the_updates():
+    X, W0, H0 = _small()
+    model = cls()(n_basis=4, n_sources=2, normalize='projection-back')
+    model.basis, model.activation = W0.copy(), H0.copy()
+    with pytest.raises(ValueError, match="Choose 'power'"):
+        model(X, iteration=1)
+    W, H = fm.update_nmf(X, W0, H0, *fm.initial_state(3, 2, 17)[::-1])
+    assert rel(model.basis, W) < 1e-9  # the updates ran before the error
+
+
+def test_singular_diagonalizer_in_separate():
+    X, W0, H0 = _small()
+    model = cls()(n_basis=4, n_sources=2)
+    model.basis, model.activation = W0.copy(), H0.copy()
+    model(X, iteration=1)
+    Q = np.array(model.diagonalizer)
+    Q[3] = 0
+    model.diagonalizer = Q
+    with pytest.raises(np.linalg.LinAlgError):
+        model.separate(X)
+
+
+def test_repr():
+    X, _, _ = _small()
+    model = cls()(n_basis=4, n_sources=2)
+    assert repr(model) == "FastMNMF(n_basis=4, n_sources=2, partitioning=False, normalize=power)"
+    model(X, iteration=0)
+    assert repr(model) == "FastMNMF(n_basis=4, n_sources=2, n_channels=3, partitioning=False, normalize=power)"
+
+
+@pytest.mark.parametrize("M,N,K", [(1, 1, 4), (9, 4, 4), (3, 9, 4), (3, 2, 65), (3, 2, 0)])
+def test_out_of_range_sizes(M, N, K):
+    rng = np.random.default_rng(0)
+    X = rng.standard_normal((M, 9, 32)) + 0j
+    with pytest.raises(ValueError, match="n_channels <= 8"):
+        cls()(n_basis=K, n_sources=N)(X, iteration=1)
+
+
+def _run(X, W0, H0, n_iter, callbacks=None, **kw):
+    model = cls()(n_basis=W0.shape[-1], n_sources=W0.shape[-3], callbacks=callbacks, **kw)
+    model.basis, model.activation = W0.copy(), H0.copy()
+    Y = model(X, iteration=n_iter)
+    return model, Y
+
+
+def test_iterate_is_bit_identical_to_the_step_loop():
+    X, W0, H0 = _small(M=4, N=3, K=10, T=256)
+    fast, Yf = _run(X, W0, H0, 6)
+    slow, Ys = _run(X, W0, H0, 6, callbacks=lambda m: None)
+    assert np.array_equal(Yf, Ys)
+    assert np.array_equal(np.asarray(fast.loss), np.asarray(slow.loss))
+    for a in ATTRS:
+        assert np.array_equal(getattr(fast, a), getattr(slow, a)), a
+    nl_fast, _ = _run(X, W0, H0, 6, recordable_loss=False)
+    nl_slow, _ = _run(X, W0, H0, 6, recordable_loss=False, callbacks=lambda m: None)
+    for a in ATTRS:
+        assert np.array_equal(getattr(nl_fast, a), getattr(fast, a)), a
+        assert np.array_equal(getattr(nl_slow, a), getattr(fast, a)), a
+
+
+def test_batch_is_bit_identical_to_single_calls_and_runs_repeat():
+    Xs, Ws, Hs = [], [], []
+    for b in range(3):
+        X, W0, H0 = _small(M=4, N=4, K=4, T=128, seed=20 + b)
+        Xs.append(X), Ws.append(W0), Hs.append(H0)
+    mb, Yb = _run(np.stack(Xs), np.stack(Ws), np.stack(Hs), 5)
+    assert Yb.shape == (3, 4, 17, 128)
+    lb = np.asarray(mb.loss)
+    for b in range(3):
+        m1, Y1 = _run(Xs[b], Ws[b], Hs[b], 5)
+        assert np.array_equal(Yb[b], Y1)
+        assert np.array_equal(lb[:, b], np.asarray(m1.loss))
+        m2, Y2 = _run(Xs[b], Ws[b], Hs[b], 5)
+        assert np.array_equal(Y1, Y2)
+
+
+def test_device_tensor_in_device_tensor_out():
+    import torch
+    X, W0, H0 = _small()
+    Xd = torch.from_numpy(X).to("cuda")
+    model, Y = _run(Xd, W0, H0, 2)
+    assert isinstance(Y, torch.Tensor) and Y.is_cuda and tuple(Y.shape) == (2, 17, 96)
+    _, Yn = _run(X, W0, H0, 2)
+    assert np.array_equal(Y.cpu().numpy(), Yn)
+
+
+def test_basis_edit_reaches_the_device():
+    X, W0, H0 = _small()
+    model, _ = _run(X, W0, H0, 1)
+    model.basis[...] *= 2.0
+    W = np.array(model.basis)
+    H = np.array(model.activation)
+    model(X, iteration=0)
+    Q, g = fm.initial_state(3, 2, 17)
+    assert abs(model.loss[-1] - fm.loss(X, W, H, g, Q)) / abs(model.loss[-1]) < 1e-9
+
+
+@pytest.mark.parametrize("K", [4, 10])
+def test_full_size_two_iterations(K):
+    rng = np.random.default_rng(K)
+    M, F, T = 4, 1025, 4096
+    X = (rng.standard_normal((M, F, T)) + 1j * rng.standard_normal((M, F, T))) * rng.random((1, F, T))
+    W0, H0 = rng.random((M, F, K)), rng.random((M, K, T))
+    model, Y = _run(X, W0, H0, 2)
+    Yr, losses, st = fm.run(X, W0, H0, 2)
+    assert np.max(np.abs(np.asarray(model.loss) - losses) / np.abs(losses)) < 1e-9
+    for a in ATTRS:
+        assert rel(getattr(model, a), st[a]) < 1e-9, a
+    assert rel(Y, Yr) < 1e-9
+    model2, Y2 = _run(X, W0, H0, 100)
+    loss = np.asarray(model2.loss)
+    assert np.all(np.isfinite(loss)) and np.all(np.isfinite(Y2))
+    assert np.all(np.diff(loss) <= 1e-9 * np.abs(loss[:-1]))
+
+
+def test_separate_refuses_inputs_that_do_not_fit_the_model():
+    """separate() reads the fitted model with the input's sizes: an input of other sizes is a ValueError, never a read
+    past the end of the model's arrays."""
+    import torch
+    X, W0, H0 = _small()
+    model, _ = _run(X, W0, H0, 1)
+    rng = np.random.default_rng(1)
+    longer = rng.standard_normal((3, 17, 160)) + 0j        # more frames than the fitted activation
+    shorter = X[:, :, :64]
+    fewer_bins = X[:, :9]
+    more_channels = rng.standard_normal((4, 17, 96)) + 0j
+    batched = np.stack([X, X])                               # a batch on an unbatched model
+    for bad in (longer, shorter, fewer_bins, more_channels, batched):
+        with pytest.raises(ValueError):
+            model.separate(bad)
+    with pytest.raises(ValueError):
+        model.separate(torch.from_numpy(longer).to("cuda"))
+    assert np.array_equal(model.separate(X), model.estimation)  # the fitting input still works
+
+
+def test_reassigned_attributes_of_another_shape_are_refused():
+    X, W0, H0 = _small()
+    model, _ = _run(X, W0, H0, 1)
+    model.diagonalizer = np.tile(np.eye(3, dtype=complex), (9, 1, 1))  # 9 bins instead of 17
+    with pytest.raises(ValueError, match="diagonalizer"):
+        model.separate(X)
+    model, _ = _run(X, W0, H0, 1)
+    model.spatial_covariance = np.ones((2, 17, 2))
+    with pytest.raises(ValueError, match="spatial_covariance"):
+        model.compute_negative_loglikelihood()
+    model, _ = _run(X, W0, H0, 1)
+    model.activation = np.ones((2, 4, 200))
+    with pytest.raises(ValueError, match="activation"):
+        model.update_once()
+
+
+def test_utterance_size_limit_is_a_value_error():
+    X = np.broadcast_to(np.zeros((1, 1, 1), dtype=complex), (2, 1 << 14, 1 << 13))  # 2^28 samples, no memory
+    with pytest.raises(ValueError, match="2\\^28"):
+        cls()(n_basis=4)(X, iteration=1)
