@@ -72,6 +72,15 @@ SIGNATURES = {
     "assx_fastmnmf_separate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_fastmnmf_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                                    _vp]),
+    "assx_mnmf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "assx_mnmf_update_basis": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_update_activation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_update_latent": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_update_spatial": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_separate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_mnmf_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_hermitian_riccati": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

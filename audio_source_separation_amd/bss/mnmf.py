@@ -1,10 +1,14 @@
-"""FastMNMF on MI355X.
+"""FastMNMF and Sawada's MNMF on MI355X (DESIGN.md sections 9 and 10).
 
 `FastMultichannelISNMF` is the drop-in for the reference class of the same name (`src/bss/mnmf.py`:
 637-946): every step of its iteration -- the NMF update of basis and activation, the spatial-covariance update, the
 diagonaliser update and the 'power' normalisation -- and its loss and `separate` run as HIP kernels
 (csrc/assx_fastmnmf.hip); without callbacks the whole loop is one library call (assx_fastmnmf_iterate).  Its output
 is `separate(input)`, (n_sources, n_bins, n_frames): the sources' images at channel `reference_id`.
+
+`MultichannelISNMF` is the drop-in for the reference class of the same name (mnmf.py:115-617, Sawada's full-rank
+MNMF): its four updates, loss and `separate` run as HIP kernels (csrc/assx_mnmf.hip), and without callbacks the loop is
+one library call (assx_mnmf_iterate).
 
 `update_diagonalizer` (mnmf.py:848-888) is also offered as a free function for callers that keep their NMF model
 elsewhere: a weighted covariance per CHANNEL m -- weights R[f,t,m] = sum_n Lambda[n,f,t] g[n,f,m] -- followed by the
@@ -388,6 +392,308 @@ class FastMultichannelISNMF(DeviceState):
 
     def separate(self, input):
         """mnmf.py:919-946: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
+        eng = self._ensure_engine()
+        X = to_device(input, eng.prec.cplx, eng.dev)
+        batched = X.dim() == 4
+        if not batched:
+            X = X.unsqueeze(0)
+        Y = self._separate_dev(X.contiguous())
+        if isinstance(input, torch.Tensor):
+            return Y if batched else Y[0]
+        Y = to_numpy(Y, np.complex128)
+        return Y if batched else Y[0]
+
+
+class MultichannelISNMF(DeviceState):
+    """
+    Reference: Sawada's MNMF, "Multichannel Extensions of Non-Negative Matrix Factorization With Complex-Valued Data"
+    (mnmf.py:115-617).  Supported: author='Sawada', float64, 2 <= n_channels <= 8, 1 <= n_sources <= 8,
+    1 <= n_basis <= 64 and n_channels * n_bins * n_frames < 2^28.
+
+    `basis` (n_bins, n_basis), `activation` (n_basis, n_frames), `latent` (n_sources, n_basis), `spatial`
+    (n_bins, n_sources, n_channels, n_channels) complex and `estimation` (n_sources, n_bins, n_frames) live on the
+    device and read as NumPy arrays.  A leading utterance axis on the input, (B, n_channels, n_bins, n_frames), adds
+    one to every attribute and to the output.  The loss is the exact value of the reference's log-det divergence
+    (DESIGN.md section 10): the reference's own value carries about 1e-6 relative noise from an eigenvalue solver.
+    """
+    basis = DeviceArray("Tb", complex_=False)
+    activation = DeviceArray("V", complex_=False)
+    latent = DeviceArray("Z", complex_=False)
+    spatial = DeviceArray("H", complex_=True)
+    estimation = DeviceArray("Y", complex_=True)
+
+    MAX_CHANNELS, MAX_SOURCES, MAX_BASIS = 8, 8, 64
+
+    def __init__(self, n_basis=10, n_sources=None, normalize=True, callbacks=None, reference_id=0, author='Sawada',
+                 recordable_loss=True, eps=EPS, *, dtype='float64', device=None, **kwargs):
+        if callbacks is not None:
+            if callable(callbacks):
+                callbacks = [callbacks]
+            self.callbacks = callbacks
+        else:
+            self.callbacks = None
+
+        self.eps = eps
+        self.n_basis = n_basis
+        self.n_sources = n_sources
+
+        self.input = None
+        self.recordable_loss = recordable_loss
+        if self.recordable_loss:
+            self.loss = LazyLossList()
+        else:
+            self.loss = None
+
+        self.normalize = normalize
+
+        if not isinstance(author, str) or author.lower() not in ('sawada', 'ozerov'):
+            raise ValueError("Choose from ['sawada', 'ozerov']")
+        if author.lower() != 'sawada':
+            raise ValueError("MultichannelISNMF: only Sawada's MNMF is supported (the reference marks Ozerov's as in "
+                             "progress)")
+        self.author = author
+
+        if set(kwargs) != set():
+            raise ValueError("Invalid keywords.")
+        self.reference_id = reference_id
+        if not isinstance(reference_id, (int, np.integer)) or reference_id < 0:
+            raise ValueError("reference_id must be a non-negative int, got {!r}".format(reference_id))
+
+        if str(dtype) not in ('float64', 'double', 'complex128'):
+            raise ValueError("MultichannelISNMF supports float64 only, got dtype={!r}".format(dtype))
+        self.dtype = 'float64'
+        self.device = device
+        self._engine = None
+        self._ws = None
+        self._ws_key = None
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            self._engine = Engine(dtype=self.dtype, device=self.device)
+        return self._engine
+
+    def _reset(self, **kwargs):
+        """mnmf.py:47-61, 183-240: latent, spatial, basis and activation are drawn (in that order) only when absent."""
+        assert self.input is not None, "Specify data!"
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+        X = self.input
+        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
+        if ndim not in (3, 4):
+            raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
+        shape = tuple(int(d) for d in (X.shape if isinstance(X, torch.Tensor) else np.shape(X)))
+        B, n_channels, n_bins, n_frames = (1,) * (4 - ndim) + shape
+
+        n_sources = self.n_sources
+        if n_sources is None:
+            n_sources = n_channels
+        n_basis = self.n_basis
+        # the limits are checked before anything is uploaded
+        if not (2 <= n_channels <= self.MAX_CHANNELS and 1 <= n_sources <= self.MAX_SOURCES
+                and 1 <= n_basis <= self.MAX_BASIS):
+            raise ValueError("MultichannelISNMF supports 2 <= n_channels <= {}, 1 <= n_sources <= {} and "
+                             "1 <= n_basis <= {}; got n_channels={}, n_sources={}, n_basis={}".format(
+                                 self.MAX_CHANNELS, self.MAX_SOURCES, self.MAX_BASIS, n_channels, n_sources, n_basis))
+        if n_channels * n_bins * n_frames >= 1 << 28:
+            raise ValueError("MultichannelISNMF: one utterance must stay below 2^28 samples (n_channels * n_bins * "
+                             "n_frames < 268435456); got {} x {} x {}".format(n_channels, n_bins, n_frames))
+        if not 0 <= self.reference_id < n_channels:
+            raise ValueError("reference_id must be in [0, {}), got {}".format(n_channels, self.reference_id))
+        self.n_sources, self.n_channels = n_sources, n_channels
+        self.n_bins, self.n_frames = n_bins, n_frames
+
+        eng = self._ensure_engine()
+        self._batched = ndim == 4
+        Xd = to_device(X, eng.prec.cplx, eng.dev)
+        if not self._batched:
+            Xd = Xd.unsqueeze(0)
+        self._X = Xd.contiguous()
+
+        lead = (B,) if self._batched else ()
+        eps = self.eps
+        if not hasattr(self, 'latent'):
+            Z = np.random.rand(*(lead + (n_sources, n_basis))) * 1e-2 + 1 / n_sources
+            Zsum = Z.sum(axis=-2, keepdims=True)
+            Zsum[Zsum < eps] = eps
+            self.latent = Z / Zsum
+        if not hasattr(self, 'spatial'):
+            self.spatial = np.tile(np.eye(n_channels, dtype=np.complex128), lead + (n_bins, n_sources, 1, 1))
+        if not hasattr(self, 'basis'):
+            self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
+        if not hasattr(self, 'activation'):
+            self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
+        # the kernels take pointers and sizes: a warm-start array of another shape would be read past its end
+        shapes = {"Z": ("latent", (B, n_sources, n_basis), False), "H": ("spatial", (B, n_bins, n_sources,
+                                                                                     n_channels, n_channels), True),
+                  "Tb": ("basis", (B, n_bins, n_basis), False), "V": ("activation", (B, n_basis, n_frames), False)}
+        for name, (attr, shp, cplx) in shapes.items():
+            got = tuple(self._dev(name, cplx).shape)
+            if got != shp:
+                raise ValueError("{}: expected shape {}, got {}".format(attr, shp[0 if self._batched else 1:],
+                                                                      got[0 if self._batched else 1:]))
+            # warm-start values are copied (mnmf.py:212-233): the model never writes into the caller's arrays
+            self._set_dev(name, self._dev(name, cplx).contiguous().clone())
+
+        key = (B, n_channels, n_sources, n_bins, n_frames, n_basis)
+        if self._ws_key != key:
+            self._ws = eng.mnmf_workspace(*key)
+            self._ws_key = key
+        self._status = eng.new_status(B)
+
+    def _model(self):
+        return self._dev("Tb", False), self._dev("V", False), self._dev("Z", False), self._dev("H", True)
+
+    def _loss_dev(self):
+        Tb, V, Z, H = self._model()
+        return self._engine.mnmf_loss(self._X, Tb, V, Z, H, self._ws, eps=self.eps, status=self._status)
+
+    def _record_loss(self):
+        loss = self._loss_dev()
+        if isinstance(self.loss, LazyLossList):
+            self.loss.append_device(loss, self._batched)
+        else:
+            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+
+    def _check_status(self):
+        if int(self._status.max().item()) & _lib.STATUS_SINGULAR:
+            self._status.zero_()
+            raise np.linalg.LinAlgError("Singular matrix")
+
+    def _run_callbacks(self):
+        if self.callbacks is not None:
+            self._check_status()
+            self._set_dev("Y", self._separate_dev(self._X))
+            for callback in self.callbacks:
+                callback(self)
+
+    # ---- the loop ----------------------------------------------------------------------------------------------------
+    def __call__(self, input, iteration=100, **kwargs):
+        """
+        Args:
+            input (n_channels, n_bins, n_frames)
+        Returns:
+            output (n_sources, n_bins, n_frames)
+        """
+        self.input = input
+
+        self._reset(**kwargs)
+
+        if iteration > 0 and self._fast_loop_ok():
+            # nothing observes the model between iterations: the loop is ONE call into the library
+            # (assx_mnmf_iterate enqueues the same entry points in the same order: bit-identical to the loop below)
+            self._run_fast_loop(iteration)
+        else:
+            if self.recordable_loss:
+                self._record_loss()
+            self._run_callbacks()
+
+            for idx in range(iteration):
+                self._update_once_dev()
+
+                if self.recordable_loss:
+                    self._record_loss()
+                self._run_callbacks()
+        self._check_status()
+
+        Y = self._separate_dev(self._X)
+        self._set_dev("Y", Y)
+        if isinstance(input, torch.Tensor):
+            return Y if self._batched else Y[0]
+        return self.estimation
+
+    _OWN_STEPS = ("update_once", "_update_once_dev", "update_basis_sawada", "update_activation_sawada",
+                  "update_latent_sawada", "update_spatial_sawada", "compute_negative_loglikelihood", "_record_loss")
+
+    def _fast_loop_ok(self):
+        if self.callbacks is not None:
+            return False
+        if any(getattr(type(self), name) is not getattr(MultichannelISNMF, name) for name in self._OWN_STEPS):
+            return False
+        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
+
+    def _run_fast_loop(self, iteration):
+        eng = self._engine
+        B = int(self._X.shape[0])
+        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
+        Tb, V, Z, H = self._model()
+        eng.mnmf_iterate(iteration, self._X, Tb, V, Z, H, self._ws, normalize=bool(self.normalize), eps=self.eps,
+                         status=self._status, loss=loss)
+        self._touch("Tb", "V", "Z", "H")
+        if loss is not None:
+            self.loss.append_device_block(loss, self._batched)
+
+    def __repr__(self):
+        s = "IS-MNMF("
+        s += "n_basis={n_basis}"
+        if hasattr(self, 'n_sources'):
+            s += ", n_sources={n_sources}"
+        if hasattr(self, 'n_channels'):
+            s += ", n_channels={n_channels}"
+        s += ", normalize={normalize}"
+        s += ", author={author}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def _update_once_dev(self):
+        self.update_basis_sawada()
+        self.update_activation_sawada()
+        self.update_latent_sawada()
+        self.update_spatial_sawada()
+
+    def update_once(self):
+        """mnmf.py:291-302: the four updates, then the estimation of the new model."""
+        self._update_once_dev()
+        self._check_status()
+        self._set_dev("Y", self._separate_dev(self._X))
+
+    def update_once_sawada(self):
+        self._update_once_dev()
+
+    def update_basis_sawada(self):
+        """mnmf.py:431-451"""
+        Tb, V, Z, H = self._model()
+        self._engine.mnmf_update_basis(self._X, Tb, V, Z, H, self._ws, eps=self.eps, status=self._status)
+        self._touch("Tb")
+
+    def update_activation_sawada(self):
+        """mnmf.py:453-473"""
+        Tb, V, Z, H = self._model()
+        self._engine.mnmf_update_activation(self._X, Tb, V, Z, H, self._ws, eps=self.eps, status=self._status)
+        self._touch("V")
+
+    def update_latent_sawada(self):
+        """mnmf.py:475-497"""
+        Tb, V, Z, H = self._model()
+        self._engine.mnmf_update_latent(self._X, Tb, V, Z, H, self._ws, eps=self.eps, status=self._status)
+        self._touch("Z")
+
+    def update_spatial_sawada(self):
+        """mnmf.py:499-525"""
+        Tb, V, Z, H = self._model()
+        self._engine.mnmf_update_spatial(self._X, Tb, V, Z, H, self._ws, normalize=bool(self.normalize),
+                                         eps=self.eps, status=self._status)
+        self._touch("H")
+
+    def compute_negative_loglikelihood(self):
+        """mnmf.py:538-552, in closed form.  Syncs to return a Python float (an array of B with a batch axis)."""
+        loss = self._loss_dev()
+        if self._batched:
+            return to_numpy(loss, np.float64)
+        return np.float64(loss.item())
+
+    def _separate_dev(self, X):
+        Tb, V, Z, H = self._model()
+        status = self._engine.new_status(int(X.shape[0]))
+        Y = self._engine.mnmf_separate(X, Tb, V, Z, H, ref=self.reference_id, eps=self.eps, status=status)
+        if int(status.max().item()) & _lib.STATUS_SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return Y
+
+    def separate(self, input):
+        """mnmf.py:554-583: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
         eng = self._ensure_engine()
         X = to_device(input, eng.prec.cplx, eng.dev)
         batched = X.dim() == 4

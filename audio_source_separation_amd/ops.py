@@ -466,6 +466,107 @@ class Engine:
                                                   ptr(ws), B, M, N, F, T, K, self.prec.code, self._st()),
                     "assx_fastmnmf_iterate")
 
+    # ------------------------------------------------------------------ MultichannelISNMF (bss/mnmf.py)
+    def _mnmf_dims(self, X, Tb, V, Z, H, ws=None):
+        """Sizes of an MNMF call, with every array checked against them (the kernels take pointers and sizes: an array
+        of another shape would be read past its end).  Refused with ValueError before any launch."""
+        if X.dim() != 4 or Z.dim() != 3:
+            raise ValueError("MNMF: expected X (B,M,F,T) and latent (B,N,K), got %s and %s"
+                             % (tuple(X.shape), tuple(Z.shape)))
+        B, M, F, T = (int(d) for d in X.shape)
+        N, K = int(Z.shape[1]), int(Z.shape[2])
+        want = {"input": (X, (B, M, F, T)), "basis": (Tb, (B, F, K)), "activation": (V, (B, K, T)),
+                "latent": (Z, (B, N, K)), "spatial": (H, (B, F, N, M, M))}
+        for name, (a, shape) in want.items():
+            dt = torch.complex128 if name in ("input", "spatial") else torch.float64
+            if a.dtype != dt or a.device != self.dev:
+                raise ValueError("MNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
+            if tuple(a.shape) != shape or not a.is_contiguous():
+                raise ValueError("MNMF: %s has shape %s, but the input %s needs %s (contiguous)"
+                                 % (name, tuple(a.shape), (B, M, F, T), shape))
+        if ws is not None:
+            need = self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64)
+            if need == 0 or ws.numel() < need:
+                raise ValueError("MNMF: workspace of %d bytes, %d needed for B=%d M=%d N=%d F=%d T=%d K=%d"
+                                 % (ws.numel(), need, B, M, N, F, T, K))
+        return B, M, N, F, T, K
+
+    def mnmf_workspace(self, B, M, N, F, T, K):
+        n = self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64)
+        if n == 0:
+            raise ValueError("MNMF supports float64, 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; "
+                             "got n_channels=%d, n_sources=%d, n_basis=%d" % (M, N, K))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def _mnmf_step(self, fn, what, X, Tb, V, Z, H, ws, eps, status):
+        B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
+        self._fastmnmf_need(status, B, "status")
+        self._check(fn(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), float(eps), ptr(status), ptr(ws), B, M, N, F,
+                       T, K, _lib.F64, self._st()), what)
+
+    def mnmf_update_basis(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
+        self._mnmf_step(self._L.assx_mnmf_update_basis, "assx_mnmf_update_basis", X, Tb, V, Z, H, ws, eps, status)
+
+    def mnmf_update_activation(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
+        self._mnmf_step(self._L.assx_mnmf_update_activation, "assx_mnmf_update_activation", X, Tb, V, Z, H, ws, eps,
+                        status)
+
+    def mnmf_update_latent(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
+        self._mnmf_step(self._L.assx_mnmf_update_latent, "assx_mnmf_update_latent", X, Tb, V, Z, H, ws, eps, status)
+
+    def mnmf_update_spatial(self, X, Tb, V, Z, H, ws, normalize=True, eps=1e-12, status=None):
+        B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
+        self._fastmnmf_need(status, B, "status")
+        self._check(self._L.assx_mnmf_update_spatial(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H),
+                                                     1 if normalize else 0, float(eps), ptr(status), ptr(ws), B, M, N,
+                                                     F, T, K, _lib.F64, self._st()), "assx_mnmf_update_spatial")
+
+    def mnmf_loss(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None, loss=None):
+        """loss (B,) float64: the negative log-likelihood of the model as it stands."""
+        B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
+        self._fastmnmf_need(status, B, "status")
+        loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
+        self._fastmnmf_need(loss, B, "loss")
+        self._check(self._L.assx_mnmf_loss(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), float(eps), ptr(loss),
+                                           ptr(status), ptr(ws), B, M, N, F, T, K, _lib.F64, self._st()),
+                    "assx_mnmf_loss")
+        return loss
+
+    def mnmf_separate(self, X, Tb, V, Z, H, ref=0, eps=1e-12, status=None, out=None):
+        """(B,N,F,T) complex: lam_n (H_n P x)[ref]."""
+        B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H)
+        self._fastmnmf_need(status, B, "status")
+        Y = out if out is not None else self.empty((B, N, F, T), dtype=torch.complex128)
+        self._fastmnmf_need(Y, B * N * F * T, "out")
+        self._check(self._L.assx_mnmf_separate(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), int(ref), float(eps),
+                                               ptr(Y), ptr(status), B, M, N, F, T, K, _lib.F64, self._st()),
+                    "assx_mnmf_separate")
+        return Y
+
+    def mnmf_iterate(self, n_iter, X, Tb, V, Z, H, ws, normalize=True, eps=1e-12, status=None, loss=None):
+        """loss: (n_iter + 1, B) float64 or None."""
+        B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
+        self._fastmnmf_need(loss, (int(n_iter) + 1) * B, "loss")
+        self._fastmnmf_need(status, B, "status")
+        self._check(self._L.assx_mnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Tb), ptr(V),
+                                              ptr(Z), ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), B, M, N, F,
+                                              T, K, _lib.F64, self._st()), "assx_mnmf_iterate")
+
+    def hermitian_riccati(self, A, Bm, status=None):
+        """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""
+        if A.dim() != 3 or tuple(Bm.shape) != tuple(A.shape) or A.shape[1] != A.shape[2]:
+            raise ValueError("hermitian_riccati: A and B must be (n, M, M), got %s and %s"
+                             % (tuple(A.shape), tuple(Bm.shape)))
+        for a in (A, Bm):
+            if a.dtype != torch.complex128 or a.device != self.dev or not a.is_contiguous():
+                raise ValueError("hermitian_riccati: A and B must be contiguous complex128 on %s" % self.dev)
+        n, M = int(A.shape[0]), int(A.shape[1])
+        self._fastmnmf_need(status, n, "status")
+        H = self.empty((n, M, M), dtype=torch.complex128)
+        self._check(self._L.assx_hermitian_riccati(self.ctx, ptr(A), ptr(Bm), ptr(H), ptr(status), n, M, _lib.F64,
+                                                   self._st()), "assx_hermitian_riccati")
+        return H
+
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):
         B, M, F, T = self._dims(X)

@@ -325,6 +325,53 @@ int assx_fastmnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* 
                           double eps, double threshold, double* loss, int32_t* status, void* ws,
                           int B, int M, int N, int F, int T, int K, int dtype, void* stream);
 
+/* ---- (f6) MultichannelISNMF, Sawada's full-rank MNMF (src/bss/mnmf.py:115-617) ----------------------------------------
+ * State (float64 only): X (B,M,F,T) complex, Tb (B,F,K) real = basis, V (B,K,T) real = activation, Z (B,N,K) real =
+ * latent, H (B,F,N,M,M) complex Hermitian = spatial.  X^[f,t] = sum_n lam_n H[f,n] with lam_n = sum_k Z[n,k] Tb[f,k]
+ * V[k,t], P = (X^ + eps I)^{-1}, y = P x.  Every step re-forms X^ from the parameters as they stand; P is never stored.
+ * 2 <= M <= 8, 1 <= N <= 8, 1 <= K <= 64, M*F*T < 2^28, dtype ASSX_F64 (ASSX_E_UNSUPPORTED otherwise).  `ws`
+ * (assx_mnmf_workspace_bytes) is scratch shared by one model's calls in order.  A failed Cholesky of X^ + eps I, or of
+ * a nonzero spatial weight sum A, sets ASSX_STATUS_SINGULAR.
+ *   assx_mnmf_update_basis       Tb *= sqrt(sum_t V sum_n Z a_n / sum_t V sum_n Z b_n), a_n = y^H H_n y,
+ *                                b_n = tr(P H_n), denominators < eps -> eps (mnmf.py:431-451).
+ *   assx_mnmf_update_activation  the same with sum_f Tb (mnmf.py:453-473).
+ *   assx_mnmf_update_latent      the same with sum_{f,t} Tb V, then Z /= sum_n Z (sum < eps -> eps) (mnmf.py:475-497).
+ *   assx_mnmf_update_spatial     per (f, n): A = sum_t lam_n P, C = sum_t lam_n y y^H, H <- the positive-definite
+ *                                solution of H' A H' = H C H (H' = 0 where A is exactly 0), + eps I, / trace when
+ *                                normalize == 1 (mnmf.py:499-525).
+ *   assx_mnmf_loss               loss (B,) float64: the exact value of the reference's
+ *                                logdet_divergence(to_PSD(X^) + eps I, to_PSD(x x^H) + eps I) summed over (f, t).
+ *   assx_mnmf_separate           Y (B,N,F,T) complex = lam_n (H_n P x)[ref] (mnmf.py:554-583).
+ *   assx_mnmf_iterate            [loss] then n_iter x { basis ; activation ; latent ; spatial ; [loss] }: the loop of
+ *                                __call__ without callbacks.  loss: (n_iter + 1, B) float64 or NULL.
+ *   assx_hermitian_riccati       a batch of n problems H A H = B (A, B, H (n,M,M) complex, float64), as the spatial
+ *                                update solves them; status (n,) int32 (may be NULL) gets ASSX_STATUS_SINGULAR where
+ *                                the Cholesky of a nonzero A fails, 0 elsewhere. */
+size_t assx_mnmf_workspace_bytes(int B, int M, int N, int F, int T, int K, int dtype);
+int assx_mnmf_update_basis(assx_ctx* ctx, const void* X, void* Tb, const void* V, const void* Z, const void* H,
+                           double eps, int32_t* status, void* ws, int B, int M, int N, int F, int T, int K, int dtype,
+                           void* stream);
+int assx_mnmf_update_activation(assx_ctx* ctx, const void* X, const void* Tb, void* V, const void* Z, const void* H,
+                                double eps, int32_t* status, void* ws, int B, int M, int N, int F, int T, int K,
+                                int dtype, void* stream);
+int assx_mnmf_update_latent(assx_ctx* ctx, const void* X, const void* Tb, const void* V, void* Z, const void* H,
+                            double eps, int32_t* status, void* ws, int B, int M, int N, int F, int T, int K, int dtype,
+                            void* stream);
+int assx_mnmf_update_spatial(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const void* Z, void* H,
+                             int normalize, double eps, int32_t* status, void* ws, int B, int M, int N, int F, int T,
+                             int K, int dtype, void* stream);
+int assx_mnmf_loss(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const void* Z, const void* H,
+                   double eps, double* loss, int32_t* status, void* ws, int B, int M, int N, int F, int T, int K,
+                   int dtype, void* stream);
+int assx_mnmf_separate(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const void* Z, const void* H,
+                       int ref, double eps, void* Y, int32_t* status, int B, int M, int N, int F, int T, int K,
+                       int dtype, void* stream);
+int assx_mnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* X, void* Tb, void* V, void* Z, void* H,
+                      double eps, double* loss, int32_t* status, void* ws, int B, int M, int N, int F, int T, int K,
+                      int dtype, void* stream);
+int assx_hermitian_riccati(assx_ctx* ctx, const void* A, const void* Bm, void* H, int32_t* status, int n, int M,
+                           int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
