@@ -35,6 +35,12 @@ CASES = (
     (6, 4, 3, "power", 17, 96),
     (8, 8, 2, "power", 11, 96),
     (3, 2, 4, False, 17, 128),
+    # the corners of the size envelope (appended: the seeds and bytes of the files above do not change); T shrinks
+    # with N * K so that five copies of the (N, K, T) activation stay under the 1 MiB a committed file may have
+    (5, 6, 17, "power", 9, 80),
+    (7, 7, 33, "power", 7, 48),
+    (8, 8, 64, "power", 5, 32),
+    (3, 1, 4, "power", 9, 100),
 )
 
 

@@ -36,6 +36,14 @@ CASES = (
     (2, 3, 4, True, 17, 96, False),
     (8, 4, 2, True, 9, 64, False),
     (3, 2, 4, True, 17, 96, True),
+    # the corners of the size envelope (appended: the seeds and bytes of the files above do not change).  F and T of
+    # the last one were picked by the restatement's own sensitivity: at T = 96 a one-ulp change of the initial basis
+    # moves the spatial model by 4e-11 after 5 iterations (restatement against itself), at T = 100 by 1e-14.
+    (5, 5, 17, True, 9, 100, False),
+    (6, 7, 33, True, 7, 80, False),
+    (7, 8, 64, True, 5, 65, False),
+    (3, 1, 4, True, 9, 100, False),
+    (8, 2, 20, True, 9, 100, False),
 )
 RICCATI_M = (2, 3, 4, 5, 6, 7, 8)
 RICCATI_BATCH = 16

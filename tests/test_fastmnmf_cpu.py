@@ -11,6 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import fastmnmf_np as fm  # noqa: E402
+import envelope_np as env  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "fastmnmf")
 FILES = sorted(glob.glob(os.path.join(GOLDEN, "*.npz")))
@@ -28,7 +29,7 @@ def load(name):
 
 
 def test_fixtures_present():
-    assert len(FILES) == 8
+    assert len(FILES) == 12
     for f in FILES:
         assert os.path.getsize(f) < 1 << 20
 
@@ -45,17 +46,40 @@ def test_restatement_matches_reference(name):
 
     Y, losses, _ = fm.run(g["X"], g["W0"], g["H0"], 20, normalize=normalize, record=record)
     scale = np.max(np.abs(g["loss"]))
-    assert np.max(np.abs(np.asarray(losses) - g["loss"])) / scale < 1e-12
+    lerr = np.abs(np.asarray(losses) - g["loss"]) / scale
+    # an ill-conditioned trajectory (envelope_np.FASTMNMF_ILL_CONDITIONED): the usual tolerances up to iteration 10,
+    # 256 x the restatement's own one-ulp sensitivity after it
+    late, late_loss = {}, np.zeros(21)
+    if name in env.FASTMNMF_ILL_CONDITIONED:
+        d, dl = env.fastmnmf_trajectory_sensitivity(g)
+        late = {a: env.FACTOR * v for a, v in d.items()}
+        late_loss[env.LAST_STABLE_ITERATION + 1:] = env.FACTOR * dl[env.LAST_STABLE_ITERATION + 1:]
+    assert np.all(lerr < np.maximum(1e-12, late_loss)), lerr
     for i in (1, 2, 5, 20):
         # summation order alone moves the 20-iteration state by up to 4.2e-12 (diagonalizer, m4_n3_k2): 1e-11 there
         tol = 1e-12 if i <= 5 else 1e-11
         for a in ATTRS:
-            assert rel(snaps[i][a], g["%s_%d" % (a, i)]) < tol, (i, a)
+            assert rel(snaps[i][a], g["%s_%d" % (a, i)]) < (max(tol, late.get(a, 0)) if i == 20 else tol), (i, a)
         if i < 20:
             s = snaps[i]
             est = fm.separate(g["X"], s["basis"], s["activation"], s["spatial_covariance"], s["diagonalizer"])
             assert rel(est, g["estimation_%d" % i]) < 1e-12, i
-    assert rel(Y, g["output"]) < 1e-11
+    assert rel(Y, g["output"]) < max(1e-11, late.get("output", 0))
+
+
+def test_only_ill_conditioned_fixtures_are_listed_as_such():
+    """A fixture is on envelope_np.FASTMNMF_ILL_CONDITIONED exactly when the restatement ALONE, run again from a basis
+    changed by one ulp, ends somewhere else after 20 iterations; up to iteration 10 all of them are stable."""
+    for name in NAMES:
+        g = load(name)
+        d, dl = env.fastmnmf_trajectory_sensitivity(g)
+        worst = max(d.values())
+        print("%-28s 20 iterations: %.1e" % (name, worst))
+        assert (worst > 1e-7) == (name in env.FASTMNMF_ILL_CONDITIONED), (name, d)
+        assert worst < 1e-10 or worst > 1e-7, (name, d)  # nothing in between: the list is not a matter of taste
+        assert np.all(dl[:env.LAST_STABLE_ITERATION + 1] < 1e-13), (name, dl)
+        d10, _ = env.fastmnmf_trajectory_sensitivity(g, env.LAST_STABLE_ITERATION)
+        assert max(d10.values()) < 1e-11, (name, d10)
 
 
 def test_initial_draw_is_the_reference_rng_order():

@@ -27,7 +27,7 @@ def load(name):
 
 
 def test_fixtures_present():
-    assert len(FILES) == 8
+    assert len(FILES) == 13
     for f in FILES + [os.path.join(GOLDEN, "riccati.npz")]:
         assert os.path.getsize(f) < 1 << 20
 
