@@ -12,6 +12,7 @@ since it was handed out) do nothing, like edits of any copy.
 """
 import numpy as np
 
+from . import _lib
 from ._device import to_device, to_numpy, torch
 
 
@@ -187,6 +188,19 @@ class DeviceState:
     """Mixin with the device side of DeviceArray attributes."""
 
     _batched = False
+
+    def _ensure_engine(self):
+        if self._engine is None:
+            from .ops import Engine  # on first use: importing this module does not import ops
+            self._engine = Engine(dtype=self.dtype, device=self.device)
+        return self._engine
+
+    def _check_status(self):
+        """Turn device-side flags into the exceptions NumPy would have raised (one sync)."""
+        flags = int(self._status.max().item())
+        if flags & _lib.STATUS_SINGULAR:
+            self._status.zero_()
+            raise np.linalg.LinAlgError("Singular matrix")
 
     def _has(self, name):
         return name in self.__dict__.get("_arrays", {})

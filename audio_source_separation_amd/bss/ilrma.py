@@ -23,7 +23,6 @@ from .._device import to_device, to_numpy, torch
 from .._state import DeviceArray, DeviceState
 from .._loss import LazyLossList
 from .. import _lib
-from ..ops import Engine
 
 EPS = 1e-12
 THRESHOLD = 1e+12
@@ -74,11 +73,6 @@ class ILRMAbase(DeviceState):
     def _require_supported(self):
         if self.algorithm_spatial not in ('IP', 'IP1', 'ISS', 'IP2', 'pairwise'):
             raise NotImplementedError("algorithm_spatial='{}' is not on the HIP path (no CPU fallback is provided).".format(self.algorithm_spatial))
-
-    def _ensure_engine(self):
-        if self._engine is None:
-            self._engine = Engine(dtype=self.dtype, device=self.device)
-        return self._engine
 
     def _upload_input(self):
         eng = self._ensure_engine()
@@ -238,13 +232,6 @@ class ILRMAbase(DeviceState):
 
     def compute_negative_loglikelihood(self):
         raise NotImplementedError("Implement 'compute_negative_loglikelihood' function.")
-
-    def _check_status(self):
-        """Turn device-side flags into the exceptions NumPy would have raised (one sync)."""
-        flags = int(self._status.max().item())
-        if flags & _lib.STATUS_SINGULAR:
-            self._status.zero_()
-            raise np.linalg.LinAlgError("Singular matrix")
 
     def _run_callbacks(self):
         if self.callbacks is not None:

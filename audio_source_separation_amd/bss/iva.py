@@ -17,7 +17,6 @@ from .._device import to_device, to_numpy, torch
 from .._state import DeviceArray, DeviceState
 from .._loss import LazyLossList
 from .. import _lib
-from ..ops import Engine
 
 EPS = 1e-12
 THRESHOLD = 1e+12
@@ -50,11 +49,6 @@ class IVAbase(DeviceState):
         self.device = device
         self._engine = None
         self._estimation = None
-
-    def _ensure_engine(self):
-        if self._engine is None:
-            self._engine = Engine(dtype=self.dtype, device=self.device)
-        return self._engine
 
     def _reset(self, **kwargs):
         assert self.input is not None, "Specify data!"
@@ -151,12 +145,6 @@ class IVAbase(DeviceState):
 
     def compute_negative_loglikelihood(self):
         raise NotImplementedError("Implement 'compute_negative_loglikelihood' function.")
-
-    def _check_status(self):
-        flags = int(self._status.max().item())
-        if flags & _lib.STATUS_SINGULAR:
-            self._status.zero_()
-            raise np.linalg.LinAlgError("Singular matrix")
 
 
 class AuxIVAbase(IVAbase):

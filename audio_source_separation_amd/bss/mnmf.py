@@ -21,7 +21,6 @@ from .._loss import LazyLossList
 from .._state import DeviceArray, DeviceState
 from .. import _lib
 from ..algorithm.projection_back import _engine
-from ..ops import Engine
 
 EPS = 1e-12
 THRESHOLD = 1e+12
@@ -77,29 +76,28 @@ def update_diagonalizer(input, diagonalizer, spatial_covariance, variance=None, 
     return Q if batched else Q[0]
 
 
-class FastMultichannelISNMF(DeviceState):
+class MultichannelNMFbase(DeviceState):
     """
-    Reference: "Fast Multichannel Source Separation Based on Jointly Diagonalizable Spatial Covariance Matrices"
-    (mnmf.py:637-946).  Supported: 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64.
+    What the multichannel NMF models share (reference: mnmf.py:25-113): the constructor state, the parsing, limits and
+    upload of the input, the warm-start check, the workspace cache, the loss record, `separate` and the loop.
 
-    `basis` (n_sources, n_bins, n_basis), `activation` (n_sources, n_basis, n_frames), `spatial_covariance`
-    (n_sources, n_bins, n_channels), `diagonalizer` (n_bins, n_channels, n_channels), `latent` and `estimation` live on
-    the device and read as NumPy arrays (an in-place edit reaches the next kernel).  A leading utterance axis on the
-    input, (B, n_channels, n_bins, n_frames), adds one to every attribute and to the output.  One utterance must stay
-    below 2^28 samples (n_channels * n_bins * n_frames).  Arrays that do not fit the input -- a `separate` input of
-    other sizes than the fitted model, a reassigned attribute of another shape -- raise ValueError.
+    A model supplies its DeviceArray attributes and
+        _reset(**kwargs)        the initial draws, built from the helpers below in the model's own order
+        _update_once_dev()      one iteration in the step loop
+        _run_fast_loop(n)       the whole loop as ONE library call
+        _loss_dev()             the loss (B,) as a float64 device tensor
+        _separate_dev(X)        the sources' images (B, n_sources, n_bins, n_frames) at channel `reference_id`
+        _OWN_STEPS              the methods whose override sends the loop back to the step loop
     """
-    basis = DeviceArray("W", complex_=False)
-    activation = DeviceArray("H", complex_=False)
-    spatial_covariance = DeviceArray("g", complex_=False)
-    diagonalizer = DeviceArray("Q", complex_=True)
-    latent = DeviceArray("Z", complex_=False)
-    estimation = DeviceArray("Y", complex_=True)
-
     MAX_CHANNELS, MAX_SOURCES, MAX_BASIS = 8, 8, 64
 
-    def __init__(self, n_basis=10, n_sources=None, partitioning=False, normalize='power', reference_id=0, callbacks=None,
-                 recordable_loss=True, eps=EPS, threshold=THRESHOLD, *, dtype='float64', device=None):
+    _LABEL = None                  # the model's name in the messages of the limit checks
+    _SAMPLES_NOTE = ""             # follows "n_frames < 268435456" in the message of the 2^28 limit
+    _CALLBACKS_BEFORE_LOOP = True  # mnmf.py:80-82; FastMNMF's own __call__ (mnmf.py:691-735) has no such call
+    _OWN_STEPS = ()
+
+    def __init__(self, n_basis=10, n_sources=None, callbacks=None, reference_id=0, recordable_loss=True, eps=EPS, *,
+                 dtype='float64', device=None):
         if callbacks is not None:
             if callable(callbacks):
                 callbacks = [callbacks]
@@ -118,32 +116,22 @@ class FastMultichannelISNMF(DeviceState):
         else:
             self.loss = None
 
-        self.partitioning = partitioning
-        self.normalize = normalize
         self.reference_id = reference_id
-
-        self.threshold = threshold
 
         self.dtype = dtype
         self.device = device
         self._engine = None
         self._ws = None
         self._ws_key = None
-        self._xt_src = None
 
-    def _ensure_engine(self):
-        if self._engine is None:
-            self._engine = Engine(dtype=self.dtype, device=self.device)
-        return self._engine
-
-    def _reset(self, **kwargs):
-        """mnmf.py:47-61, 653-689: Q and g are reset on every call; basis / activation (and latent) only when absent."""
+    # ---- the pieces of _reset ----------------------------------------------------------------------------------------
+    def _parse_input(self, **kwargs):
+        """mnmf.py:49-63: keywords become attributes; (batched, B, n_channels, n_bins, n_frames, n_sources) of the input."""
         assert self.input is not None, "Specify data!"
 
         for key in kwargs.keys():
             setattr(self, key, kwargs[key])
 
-        eng = self._ensure_engine()
         X = self.input
         ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
         if ndim not in (3, 4):
@@ -154,25 +142,185 @@ class FastMultichannelISNMF(DeviceState):
         n_sources = self.n_sources
         if n_sources is None:
             n_sources = n_channels
-        self.n_sources, self.n_channels = n_sources, n_channels
-        self.n_bins, self.n_frames = n_bins, n_frames
-        n_basis = self.n_basis
-        # the limits are checked before the input is uploaded
+        return ndim == 4, B, n_channels, n_bins, n_frames, n_sources
+
+    def _check_limits(self, n_channels, n_sources, n_bins, n_frames):
+        """Raises before anything is uploaded."""
+        label, n_basis = self._LABEL, self.n_basis
         if not (2 <= n_channels <= self.MAX_CHANNELS and 1 <= n_sources <= self.MAX_SOURCES
                 and 1 <= n_basis <= self.MAX_BASIS):
-            raise ValueError("FastMultichannelISNMF supports 2 <= n_channels <= {}, 1 <= n_sources <= {} and "
+            raise ValueError("{} supports 2 <= n_channels <= {}, 1 <= n_sources <= {} and "
                              "1 <= n_basis <= {}; got n_channels={}, n_sources={}, n_basis={}".format(
-                                 self.MAX_CHANNELS, self.MAX_SOURCES, self.MAX_BASIS, n_channels, n_sources, n_basis))
+                                 label, self.MAX_CHANNELS, self.MAX_SOURCES, self.MAX_BASIS, n_channels, n_sources,
+                                 n_basis))
         if n_channels * n_bins * n_frames >= 1 << 28:
-            raise ValueError("FastMultichannelISNMF: one utterance must stay below 2^28 samples (n_channels * n_bins * "
-                             "n_frames < 268435456: 4 GiB in complex128); got {} x {} x {}".format(
-                                 n_channels, n_bins, n_frames))
+            raise ValueError("{}: one utterance must stay below 2^28 samples (n_channels * n_bins * "
+                             "n_frames < 268435456{}); got {} x {} x {}".format(label, self._SAMPLES_NOTE, n_channels,
+                                                                                 n_bins, n_frames))
 
-        self._batched = ndim == 4
-        Xd = to_device(X, eng.prec.cplx, eng.dev)
+    def _set_sizes(self, n_channels, n_sources, n_bins, n_frames):
+        self.n_sources, self.n_channels = n_sources, n_channels
+        self.n_bins, self.n_frames = n_bins, n_frames
+
+    def _upload_input(self, batched):
+        eng = self._ensure_engine()
+        self._batched = batched
+        Xd = to_device(self.input, eng.prec.cplx, eng.dev)
         if not self._batched:
             Xd = Xd.unsqueeze(0)
         self._X = Xd.contiguous()
+
+    def _check_warm_start(self, table, copy=False):
+        """table: (device name, attribute name, expected shape with the utterance axis, complex) per array.  The
+        kernels take pointers and sizes: a warm-start array of another shape would be read past its end.  copy: the
+        model owns its arrays afterwards, so it never writes into the caller's."""
+        lead = 0 if self._batched else 1
+        for name, attr, shape, cplx in table:
+            got = tuple(self._dev(name, cplx).shape)
+            if got != shape:
+                raise ValueError("{}: expected shape {}, got {}".format(attr, shape[lead:], got[lead:]))
+            if copy:
+                self._set_dev(name, self._dev(name, cplx).contiguous().clone())
+
+    def _ensure_workspace(self, key, alloc):
+        """alloc(B, n_channels, n_sources, n_bins, n_frames, n_basis) runs only when `key` changes."""
+        if self._ws_key != key:
+            self._ws = alloc(*key[:6])
+            self._ws_key = key
+
+    # ---- loss, status, callbacks -----------------------------------------------------------------------------------
+    def _record_loss(self):
+        loss = self._loss_dev()
+        if isinstance(self.loss, LazyLossList):
+            self.loss.append_device(loss, self._batched)
+        else:
+            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+
+    def compute_negative_loglikelihood(self):
+        """mnmf.py:538-552 (in closed form) / 890-917.  Syncs to return a Python float (an array of B with a batch
+        axis)."""
+        loss = self._loss_dev()
+        if self._batched:
+            return to_numpy(loss, np.float64)
+        return np.float64(loss.item())
+
+    def _run_callbacks(self):
+        if self.callbacks is not None:
+            self._check_status()
+            self._set_dev("Y", self._separate_dev(self._X))
+            for callback in self.callbacks:
+                callback(self)
+
+    # ---- the loop ----------------------------------------------------------------------------------------------------
+    def __call__(self, input, iteration=100, **kwargs):
+        """
+        Args:
+            input (n_channels, n_bins, n_frames)
+        Returns:
+            output (n_sources, n_bins, n_frames)
+        """
+        self.input = input
+
+        self._reset(**kwargs)
+
+        if iteration > 0 and self._fast_loop_ok():
+            # nothing observes the model between iterations: the loop is ONE call into the library (its *_iterate entry
+            # enqueues the same entry points in the same order: bit-identical to the loop below)
+            self._run_fast_loop(iteration)
+        else:
+            if self.recordable_loss:
+                self._record_loss()
+            if self._CALLBACKS_BEFORE_LOOP:
+                self._run_callbacks()
+
+            for idx in range(iteration):
+                self._update_once_dev()
+
+                if self.recordable_loss:
+                    self._record_loss()
+                self._run_callbacks()
+        self._check_status()
+
+        Y = self._separate_dev(self._X)
+        self._set_dev("Y", Y)
+        if isinstance(input, torch.Tensor):
+            return Y if self._batched else Y[0]
+        return self.estimation
+
+    def _fast_loop_ok(self):
+        if self.callbacks is not None:
+            return False
+        owner = next(c for c in type(self).__mro__ if "_OWN_STEPS" in vars(c))  # the model a subclass derives from
+        if any(getattr(type(self), name) is not getattr(owner, name) for name in owner._OWN_STEPS):
+            return False
+        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
+
+    def _reset(self, **kwargs):
+        raise NotImplementedError("Implement '_reset' method")
+
+    def _update_once_dev(self):
+        raise NotImplementedError("Implement '_update_once_dev' method")
+
+    def update_once(self):
+        raise NotImplementedError("Implement 'update_once' method")
+
+    def separate(self, input):
+        """mnmf.py:554-583 / 919-946: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
+        eng = self._ensure_engine()
+        X = to_device(input, eng.prec.cplx, eng.dev)
+        batched = X.dim() == 4
+        if not batched:
+            X = X.unsqueeze(0)
+        Y = self._separate_dev(X.contiguous())
+        if isinstance(input, torch.Tensor):
+            return Y if batched else Y[0]
+        Y = to_numpy(Y, np.complex128)
+        return Y if batched else Y[0]
+
+
+class FastMultichannelISNMF(MultichannelNMFbase):
+    """
+    Reference: "Fast Multichannel Source Separation Based on Jointly Diagonalizable Spatial Covariance Matrices"
+    (mnmf.py:637-946).  Supported: 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64.
+
+    `basis` (n_sources, n_bins, n_basis), `activation` (n_sources, n_basis, n_frames), `spatial_covariance`
+    (n_sources, n_bins, n_channels), `diagonalizer` (n_bins, n_channels, n_channels), `latent` and `estimation` live on
+    the device and read as NumPy arrays (an in-place edit reaches the next kernel).  A leading utterance axis on the
+    input, (B, n_channels, n_bins, n_frames), adds one to every attribute and to the output.  One utterance must stay
+    below 2^28 samples (n_channels * n_bins * n_frames).  Arrays that do not fit the input -- a `separate` input of
+    other sizes than the fitted model, a reassigned attribute of another shape -- raise ValueError.
+    """
+    basis = DeviceArray("W", complex_=False)
+    activation = DeviceArray("H", complex_=False)
+    spatial_covariance = DeviceArray("g", complex_=False)
+    diagonalizer = DeviceArray("Q", complex_=True)
+    latent = DeviceArray("Z", complex_=False)
+    estimation = DeviceArray("Y", complex_=True)
+
+    _LABEL = "FastMultichannelISNMF"
+    _SAMPLES_NOTE = ": 4 GiB in complex128"
+    _CALLBACKS_BEFORE_LOOP = False
+
+    def __init__(self, n_basis=10, n_sources=None, partitioning=False, normalize='power', reference_id=0, callbacks=None,
+                 recordable_loss=True, eps=EPS, threshold=THRESHOLD, *, dtype='float64', device=None):
+        super().__init__(n_basis=n_basis, n_sources=n_sources, callbacks=callbacks, reference_id=reference_id,
+                         recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+
+        self.partitioning = partitioning
+        self.normalize = normalize
+
+        self.threshold = threshold
+
+        self._xt_src = None
+
+    def _reset(self, **kwargs):
+        """mnmf.py:47-61, 653-689: Q and g are reset on every call; basis / activation (and latent) only when absent."""
+        batched, B, n_channels, n_bins, n_frames, n_sources = self._parse_input(**kwargs)
+        eng = self._ensure_engine()
+        self._set_sizes(n_channels, n_sources, n_bins, n_frames)
+        n_basis = self.n_basis
+        self._check_limits(n_channels, n_sources, n_bins, n_frames)
+        self._upload_input(batched)
 
         Q = torch.eye(n_channels, dtype=eng.prec.cplx, device=eng.dev).repeat(B, n_bins, 1, 1)
         G = np.ones((n_sources, n_bins, n_channels)) * 1e-2
@@ -188,27 +336,21 @@ class FastMultichannelISNMF(DeviceState):
                 self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
             if not hasattr(self, 'activation'):
                 self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
-            shapes = {"Z": (B, n_sources, n_basis), "W": (B, n_bins, n_basis), "H": (B, n_basis, n_frames)}
+            table = [("Z", "latent", (B, n_sources, n_basis), False), ("W", "basis", (B, n_bins, n_basis), False),
+                     ("H", "activation", (B, n_basis, n_frames), False)]
         else:
             if not hasattr(self, 'basis'):
                 self.basis = np.random.rand(*(lead + (n_sources, n_bins, n_basis)))
             if not hasattr(self, 'activation'):
                 self.activation = np.random.rand(*(lead + (n_sources, n_basis, n_frames)))
-            shapes = {"W": (B, n_sources, n_bins, n_basis), "H": (B, n_sources, n_basis, n_frames)}
-        # the kernels take pointers and sizes: a warm-start array of another shape would be read past its end
-        names = {"Z": "latent", "W": "basis", "H": "activation"}
-        for name, shape in shapes.items():
-            got = tuple(self._dev(name, False).shape)
-            if got != shape:
-                raise ValueError("{}: expected shape {}, got {}".format(names[name], shape[0 if self._batched else 1:],
-                                                                     got[0 if self._batched else 1:]))
+            table = [("W", "basis", (B, n_sources, n_bins, n_basis), False),
+                     ("H", "activation", (B, n_sources, n_basis, n_frames), False)]
+        self._check_warm_start(table)
         self._set_dev("Q", Q.contiguous())
         self._set_dev("g", G.contiguous())
 
-        key = (B, n_channels, n_sources, n_bins, n_frames, n_basis, eng.prec.name)
-        if self._ws_key != key:
-            self._ws = eng.fastmnmf_workspace(*key[:6])
-            self._ws_key = key
+        self._ensure_workspace((B, n_channels, n_sources, n_bins, n_frames, n_basis, eng.prec.name),
+                               eng.fastmnmf_workspace)
         self._xt_src = None
         self._status = eng.new_status(B)
 
@@ -247,66 +389,14 @@ class FastMultichannelISNMF(DeviceState):
         self._xt_src = Q
         return loss
 
-    def _record_loss(self):
-        loss = self._loss_dev()
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, self._batched)
-        else:
-            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
-
-    def _check_status(self):
-        if int(self._status.max().item()) & _lib.STATUS_SINGULAR:
-            self._status.zero_()
-            raise np.linalg.LinAlgError("Singular matrix")
-
     # ---- the loop ----------------------------------------------------------------------------------------------------
-    def __call__(self, input, iteration=100, **kwargs):
-        """
-        Args:
-            input (n_channels, n_bins, n_frames)
-        Returns:
-            output (n_sources, n_bins, n_frames)
-        """
-        self.input = input
-
-        self._reset(**kwargs)
-
-        if iteration > 0 and self._fast_loop_ok():
-            # nothing observes the model between iterations: the loop is ONE call into the library
-            # (assx_fastmnmf_iterate enqueues the same entry points in the same order: bit-identical to the loop below)
-            self._run_fast_loop(iteration)
-        else:
-            if self.recordable_loss:
-                self._record_loss()
-
-            for idx in range(iteration):
-                self.update_once()
-
-                if self.recordable_loss:
-                    self._record_loss()
-
-                if self.callbacks is not None:
-                    self._check_status()
-                    self._set_dev("Y", self._separate_dev(self._X))
-                    for callback in self.callbacks:
-                        callback(self)
-        self._check_status()
-
-        Y = self._separate_dev(self._X)
-        self._set_dev("Y", Y)
-        if isinstance(input, torch.Tensor):
-            return Y if self._batched else Y[0]
-        return self.estimation
-
     _OWN_STEPS = ("update_once", "update_NMF", "update_SCM", "update_diagonalizer", "compute_negative_loglikelihood",
                   "_record_loss")
 
     def _fast_loop_ok(self):
-        if self.callbacks is not None or self.partitioning or self.normalize not in (False, None, 0, '', 'power'):
+        if self.partitioning or self.normalize not in (False, None, 0, '', 'power'):
             return False
-        if any(getattr(type(self), name) is not getattr(FastMultichannelISNMF, name) for name in self._OWN_STEPS):
-            return False
-        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
+        return super()._fast_loop_ok()
 
     def _run_fast_loop(self, iteration):
         eng = self._engine
@@ -332,6 +422,9 @@ class FastMultichannelISNMF(DeviceState):
         s += ")"
 
         return s.format(**self.__dict__)
+
+    def _update_once_dev(self):
+        self.update_once()  # the step loop runs the public method, whatever a subclass made of it
 
     def update_once(self):
         """mnmf.py:737-773"""
@@ -375,13 +468,6 @@ class FastMultichannelISNMF(DeviceState):
         self._touch("Q")
         self._xt_src = None
 
-    def compute_negative_loglikelihood(self):
-        """mnmf.py:890-917.  Syncs to return a Python float (an array of B with a batch axis)."""
-        loss = self._loss_dev()
-        if self._batched:
-            return to_numpy(loss, np.float64)
-        return np.float64(loss.item())
-
     def _separate_dev(self, X):
         W, H, g, Q = self._model()
         status = self._engine.new_status(int(X.shape[0]))
@@ -390,21 +476,8 @@ class FastMultichannelISNMF(DeviceState):
             raise np.linalg.LinAlgError("Singular matrix")
         return Y
 
-    def separate(self, input):
-        """mnmf.py:919-946: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
-        eng = self._ensure_engine()
-        X = to_device(input, eng.prec.cplx, eng.dev)
-        batched = X.dim() == 4
-        if not batched:
-            X = X.unsqueeze(0)
-        Y = self._separate_dev(X.contiguous())
-        if isinstance(input, torch.Tensor):
-            return Y if batched else Y[0]
-        Y = to_numpy(Y, np.complex128)
-        return Y if batched else Y[0]
 
-
-class MultichannelISNMF(DeviceState):
+class MultichannelISNMF(MultichannelNMFbase):
     """
     Reference: Sawada's MNMF, "Multichannel Extensions of Non-Negative Matrix Factorization With Complex-Valued Data"
     (mnmf.py:115-617).  Supported: author='Sawada', float64, 2 <= n_channels <= 8, 1 <= n_sources <= 8,
@@ -422,27 +495,12 @@ class MultichannelISNMF(DeviceState):
     spatial = DeviceArray("H", complex_=True)
     estimation = DeviceArray("Y", complex_=True)
 
-    MAX_CHANNELS, MAX_SOURCES, MAX_BASIS = 8, 8, 64
+    _LABEL = "MultichannelISNMF"
 
     def __init__(self, n_basis=10, n_sources=None, normalize=True, callbacks=None, reference_id=0, author='Sawada',
                  recordable_loss=True, eps=EPS, *, dtype='float64', device=None, **kwargs):
-        if callbacks is not None:
-            if callable(callbacks):
-                callbacks = [callbacks]
-            self.callbacks = callbacks
-        else:
-            self.callbacks = None
-
-        self.eps = eps
-        self.n_basis = n_basis
-        self.n_sources = n_sources
-
-        self.input = None
-        self.recordable_loss = recordable_loss
-        if self.recordable_loss:
-            self.loss = LazyLossList()
-        else:
-            self.loss = None
+        super().__init__(n_basis=n_basis, n_sources=n_sources, callbacks=callbacks, reference_id=reference_id,
+                         recordable_loss=recordable_loss, eps=eps, dtype='float64', device=device)
 
         self.normalize = normalize
 
@@ -455,61 +513,21 @@ class MultichannelISNMF(DeviceState):
 
         if set(kwargs) != set():
             raise ValueError("Invalid keywords.")
-        self.reference_id = reference_id
         if not isinstance(reference_id, (int, np.integer)) or reference_id < 0:
             raise ValueError("reference_id must be a non-negative int, got {!r}".format(reference_id))
 
         if str(dtype) not in ('float64', 'double', 'complex128'):
             raise ValueError("MultichannelISNMF supports float64 only, got dtype={!r}".format(dtype))
-        self.dtype = 'float64'
-        self.device = device
-        self._engine = None
-        self._ws = None
-        self._ws_key = None
-
-    def _ensure_engine(self):
-        if self._engine is None:
-            self._engine = Engine(dtype=self.dtype, device=self.device)
-        return self._engine
 
     def _reset(self, **kwargs):
         """mnmf.py:47-61, 183-240: latent, spatial, basis and activation are drawn (in that order) only when absent."""
-        assert self.input is not None, "Specify data!"
-
-        for key in kwargs.keys():
-            setattr(self, key, kwargs[key])
-
-        X = self.input
-        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
-        if ndim not in (3, 4):
-            raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
-        shape = tuple(int(d) for d in (X.shape if isinstance(X, torch.Tensor) else np.shape(X)))
-        B, n_channels, n_bins, n_frames = (1,) * (4 - ndim) + shape
-
-        n_sources = self.n_sources
-        if n_sources is None:
-            n_sources = n_channels
+        batched, B, n_channels, n_bins, n_frames, n_sources = self._parse_input(**kwargs)
         n_basis = self.n_basis
-        # the limits are checked before anything is uploaded
-        if not (2 <= n_channels <= self.MAX_CHANNELS and 1 <= n_sources <= self.MAX_SOURCES
-                and 1 <= n_basis <= self.MAX_BASIS):
-            raise ValueError("MultichannelISNMF supports 2 <= n_channels <= {}, 1 <= n_sources <= {} and "
-                             "1 <= n_basis <= {}; got n_channels={}, n_sources={}, n_basis={}".format(
-                                 self.MAX_CHANNELS, self.MAX_SOURCES, self.MAX_BASIS, n_channels, n_sources, n_basis))
-        if n_channels * n_bins * n_frames >= 1 << 28:
-            raise ValueError("MultichannelISNMF: one utterance must stay below 2^28 samples (n_channels * n_bins * "
-                             "n_frames < 268435456); got {} x {} x {}".format(n_channels, n_bins, n_frames))
+        self._check_limits(n_channels, n_sources, n_bins, n_frames)
         if not 0 <= self.reference_id < n_channels:
             raise ValueError("reference_id must be in [0, {}), got {}".format(n_channels, self.reference_id))
-        self.n_sources, self.n_channels = n_sources, n_channels
-        self.n_bins, self.n_frames = n_bins, n_frames
-
-        eng = self._ensure_engine()
-        self._batched = ndim == 4
-        Xd = to_device(X, eng.prec.cplx, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._set_sizes(n_channels, n_sources, n_bins, n_frames)
+        self._upload_input(batched)
 
         lead = (B,) if self._batched else ()
         eps = self.eps
@@ -524,22 +542,14 @@ class MultichannelISNMF(DeviceState):
             self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
         if not hasattr(self, 'activation'):
             self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
-        # the kernels take pointers and sizes: a warm-start array of another shape would be read past its end
-        shapes = {"Z": ("latent", (B, n_sources, n_basis), False), "H": ("spatial", (B, n_bins, n_sources,
-                                                                                     n_channels, n_channels), True),
-                  "Tb": ("basis", (B, n_bins, n_basis), False), "V": ("activation", (B, n_basis, n_frames), False)}
-        for name, (attr, shp, cplx) in shapes.items():
-            got = tuple(self._dev(name, cplx).shape)
-            if got != shp:
-                raise ValueError("{}: expected shape {}, got {}".format(attr, shp[0 if self._batched else 1:],
-                                                                      got[0 if self._batched else 1:]))
-            # warm-start values are copied (mnmf.py:212-233): the model never writes into the caller's arrays
-            self._set_dev(name, self._dev(name, cplx).contiguous().clone())
+        # warm-start values are copied (mnmf.py:212-233)
+        self._check_warm_start([("Z", "latent", (B, n_sources, n_basis), False),
+                                ("H", "spatial", (B, n_bins, n_sources, n_channels, n_channels), True),
+                                ("Tb", "basis", (B, n_bins, n_basis), False),
+                                ("V", "activation", (B, n_basis, n_frames), False)], copy=True)
 
-        key = (B, n_channels, n_sources, n_bins, n_frames, n_basis)
-        if self._ws_key != key:
-            self._ws = eng.mnmf_workspace(*key)
-            self._ws_key = key
+        eng = self._engine
+        self._ensure_workspace((B, n_channels, n_sources, n_bins, n_frames, n_basis), eng.mnmf_workspace)
         self._status = eng.new_status(B)
 
     def _model(self):
@@ -549,69 +559,9 @@ class MultichannelISNMF(DeviceState):
         Tb, V, Z, H = self._model()
         return self._engine.mnmf_loss(self._X, Tb, V, Z, H, self._ws, eps=self.eps, status=self._status)
 
-    def _record_loss(self):
-        loss = self._loss_dev()
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, self._batched)
-        else:
-            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
-
-    def _check_status(self):
-        if int(self._status.max().item()) & _lib.STATUS_SINGULAR:
-            self._status.zero_()
-            raise np.linalg.LinAlgError("Singular matrix")
-
-    def _run_callbacks(self):
-        if self.callbacks is not None:
-            self._check_status()
-            self._set_dev("Y", self._separate_dev(self._X))
-            for callback in self.callbacks:
-                callback(self)
-
     # ---- the loop ----------------------------------------------------------------------------------------------------
-    def __call__(self, input, iteration=100, **kwargs):
-        """
-        Args:
-            input (n_channels, n_bins, n_frames)
-        Returns:
-            output (n_sources, n_bins, n_frames)
-        """
-        self.input = input
-
-        self._reset(**kwargs)
-
-        if iteration > 0 and self._fast_loop_ok():
-            # nothing observes the model between iterations: the loop is ONE call into the library
-            # (assx_mnmf_iterate enqueues the same entry points in the same order: bit-identical to the loop below)
-            self._run_fast_loop(iteration)
-        else:
-            if self.recordable_loss:
-                self._record_loss()
-            self._run_callbacks()
-
-            for idx in range(iteration):
-                self._update_once_dev()
-
-                if self.recordable_loss:
-                    self._record_loss()
-                self._run_callbacks()
-        self._check_status()
-
-        Y = self._separate_dev(self._X)
-        self._set_dev("Y", Y)
-        if isinstance(input, torch.Tensor):
-            return Y if self._batched else Y[0]
-        return self.estimation
-
     _OWN_STEPS = ("update_once", "_update_once_dev", "update_basis_sawada", "update_activation_sawada",
                   "update_latent_sawada", "update_spatial_sawada", "compute_negative_loglikelihood", "_record_loss")
-
-    def _fast_loop_ok(self):
-        if self.callbacks is not None:
-            return False
-        if any(getattr(type(self), name) is not getattr(MultichannelISNMF, name) for name in self._OWN_STEPS):
-            return False
-        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
 
     def _run_fast_loop(self, iteration):
         eng = self._engine
@@ -677,13 +627,6 @@ class MultichannelISNMF(DeviceState):
                                          eps=self.eps, status=self._status)
         self._touch("H")
 
-    def compute_negative_loglikelihood(self):
-        """mnmf.py:538-552, in closed form.  Syncs to return a Python float (an array of B with a batch axis)."""
-        loss = self._loss_dev()
-        if self._batched:
-            return to_numpy(loss, np.float64)
-        return np.float64(loss.item())
-
     def _separate_dev(self, X):
         Tb, V, Z, H = self._model()
         status = self._engine.new_status(int(X.shape[0]))
@@ -691,16 +634,3 @@ class MultichannelISNMF(DeviceState):
         if int(status.max().item()) & _lib.STATUS_SINGULAR:
             raise np.linalg.LinAlgError("Singular matrix")
         return Y
-
-    def separate(self, input):
-        """mnmf.py:554-583: (n_sources, n_bins, n_frames), the sources' images at channel `reference_id`."""
-        eng = self._ensure_engine()
-        X = to_device(input, eng.prec.cplx, eng.dev)
-        batched = X.dim() == 4
-        if not batched:
-            X = X.unsqueeze(0)
-        Y = self._separate_dev(X.contiguous())
-        if isinstance(input, torch.Tensor):
-            return Y if batched else Y[0]
-        Y = to_numpy(Y, np.complex128)
-        return Y if batched else Y[0]

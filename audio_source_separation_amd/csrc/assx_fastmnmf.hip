@@ -6,7 +6,7 @@
 //
 //   P2  fm_bin_reduce_kernel<basis>   one workgroup per (b, f), reduce over t      W *= sqrt(num / max(den, eps))
 //   P3  fm_act_partial_kernel          (t block, f slice, b x pair chunk), reduce over an f slice
-//       fm_act_apply_kernel            slices summed in ascending order             H *= sqrt(num / max(den, eps))
+//       act_apply_kernel               slices summed in ascending order             H *= sqrt(num / max(den, eps))
 //   P4  fm_bin_reduce_kernel<scm>     one workgroup per (b, f), reduce over t      g *= sqrt(A / max(B, eps))
 //   P5  fm_mix_kernel                  R (B,M,F,T) from W, H, g;  then the covariance pass + eps-floored IP sweep of
 //                                      assx_fastmnmf_update_diagonalizer (fastmnmf_weighted_ip)
@@ -21,22 +21,13 @@
 // the waves of a workgroup in index order, then slices in index order; no float atomics), and no partition depends on
 // B: two runs give the same bits, a batch gives the bits of its single-utterance calls.
 #include "assx_common.hpp"
+#include "assx_mnmf_common.hpp"
 #include "assx_widem.hpp"
 
 using namespace assx;
+using namespace assx::mf;
 
 namespace {
-
-constexpr int NMAX = 8;     // sources
-constexpr int KMAX = 64;    // n_basis
-constexpr int CH = 16;      // (numerator, denominator) pairs a thread accumulates per chunk
-constexpr int FS_ACT = 16;  // f slices of the activation half
-constexpr int BLK = 256;    // threads of the per-bin kernels
-constexpr int ABLK = 64;    // threads (frames) of an activation-half workgroup
-
-inline unsigned nblocks(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
-
-inline int act_slices(int F) { return F < FS_ACT ? F : FS_ACT; }
 
 struct FmLayout {
   size_t xt, r2, lpart, dws, total;
@@ -64,13 +55,6 @@ __device__ __forceinline__ R pick(const R (&v)[S], int i) {  // v[i] for a run-t
 #pragma unroll
   for (int q = 1; q < S; ++q) r = (i == q) ? v[q] : r;
   return r;
-}
-
-template <typename R>
-__device__ __forceinline__ R wave_sum_down(R v) {  // fixed butterfly; the total lands in lane 0
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, WAVE);
-  return v;
 }
 
 // Lambda_n at frame t and R_m = sum_n Lambda_n g[n,m] (mnmf.py:791-793).  Wf[n * wn + k], gf[n * gn + m]: the bin's
@@ -269,14 +253,8 @@ __global__ void __launch_bounds__(BLK) fm_project_kernel(const Cx<R>* __restrict
     }
   }
   if constexpr (!LOSS) return;
-  acc = wave_sum_down(acc);
-  if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0;
-    for (int w = 0; w < BLK / WAVE; ++w) s += red[w];
-    lpart[(size_t)b * F + f] = s;
-  }
+  acc = block_sum<double, BLK / WAVE>(acc, red);
+  if (tid == 0) lpart[(size_t)b * F + f] = acc;
 }
 
 // ln|det(Q_f Q_f^T)| = ln|det Q_f|^2 per (b, f), one thread each, into the second half of lpart
@@ -300,15 +278,9 @@ __global__ void __launch_bounds__(BLK) fm_loss_finalize_kernel(const double* __r
     s += lpart[(size_t)b * F + f];
     d += lpart[(size_t)B * F + (size_t)b * F + f];
   }
-  s = wave_sum_down(s);
-  d = wave_sum_down(d);
-  if ((tid & (WAVE - 1)) == 0) red[0][tid / WAVE] = s, red[1][tid / WAVE] = d;
-  __syncthreads();
-  if (tid == 0) {
-    double ss = 0, dd = 0;
-    for (int w = 0; w < BLK / WAVE; ++w) ss += red[0][w], dd += red[1][w];
-    loss[b] = ss - (double)T * dd;
-  }
+  s = block_sum<double, BLK / WAVE>(s, red[0]);
+  d = block_sum<double, BLK / WAVE>(d, red[1]);
+  if (tid == 0) loss[b] = s - (double)T * d;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -339,9 +311,9 @@ __global__ void __launch_bounds__(BLK) fm_bin_reduce_kernel(R* __restrict__ W, c
     int pn[CH], pq[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) pn[j] = (p0 + j) / Qd, pq[j] = (p0 + j) % Qd;
-    R acc[2 * CH];
+    R num[CH], den[CH];
 #pragma unroll
-    for (int j = 0; j < 2 * CH; ++j) acc[j] = 0;
+    for (int j = 0; j < CH; ++j) num[j] = 0, den[j] = 0;
     for (int t = tid; t < T; t += BLK) {
       R x[M], lam[NMAX], Rm[M], a[M], c[M];
 #pragma unroll
@@ -355,30 +327,22 @@ __global__ void __launch_bounds__(BLK) fm_bin_reduce_kernel(R* __restrict__ W, c
         for (int j = 0; j < CH; ++j)
           if (p0 + j < NP) {
             const R h = Hb[(size_t)(p0 + j) * T + t];
-            acc[2 * j] += h * pick(gx, pn[j]);
-            acc[2 * j + 1] += h * pick(gr, pn[j]);
+            num[j] += h * pick(gx, pn[j]);
+            den[j] += h * pick(gr, pn[j]);
           }
       } else {
 #pragma unroll
         for (int j = 0; j < CH; ++j)
           if (p0 + j < NP) {
             const R l = pick(lam, pn[j]);
-            acc[2 * j] += l * pick(a, pq[j]);
-            acc[2 * j + 1] += l * pick(c, pq[j]);
+            num[j] += l * pick(a, pq[j]);
+            den[j] += l * pick(c, pq[j]);
           }
       }
     }
-#pragma unroll
-    for (int j = 0; j < 2 * CH; ++j) {
-      const R v = wave_sum_down(acc[j]);
-      if ((tid & (WAVE - 1)) == 0) red[tid / WAVE][j] = v;
-    }
-    __syncthreads();
-    if (tid < 2 * CH && p0 + tid / 2 < NP) {
-      R s = 0;
-      for (int w = 0; w < BLK / WAVE; ++w) s += red[w][tid];
-      res[2 * p0 + tid] = s;
-    }
+    R sn, sd;
+    block_pair_sums<R, BLK / WAVE>(num, den, red, sn, sd);
+    if (tid < CH && p0 + tid < NP) res[2 * (p0 + tid)] = sn, res[2 * (p0 + tid) + 1] = sd;
     __syncthreads();
   }
   for (int p = tid; p < NP; p += BLK) {
@@ -395,7 +359,7 @@ __global__ void __launch_bounds__(BLK) fm_bin_reduce_kernel(R* __restrict__ W, c
 
 // ---------------------------------------------------------------------------------------------------------------
 // P3: activation half (mnmf.py:803-813), reduce over f.  Workgroup (frame block, f slice, utterance x pair chunk);
-// the slice sums go to part (B,FS,2,N*K,T) and fm_act_apply_kernel adds them in slice order.
+// the slice sums go to part (B,FS,2,N*K,T) and act_apply_kernel adds them in slice order.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename R, int M>
 __global__ void __launch_bounds__(ABLK) fm_act_partial_kernel(const R* __restrict__ W, const R* __restrict__ H,
@@ -441,23 +405,6 @@ __global__ void __launch_bounds__(ABLK) fm_act_partial_kernel(const R* __restric
       o[0] = acc[2 * j];
       o[(size_t)NP * T] = acc[2 * j + 1];
     }
-}
-
-template <typename R>
-__global__ void __launch_bounds__(BLK) fm_act_apply_kernel(R* __restrict__ H, const R* __restrict__ part, double eps_d,
-                                                           int NP, int T, int FS, size_t total) {
-  const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
-  if (i >= total) return;
-  const R eps = (R)eps_d;
-  const size_t per = (size_t)NP * T, b = i / per, r = i % per;
-  R num = 0, den = 0;
-  for (int s = 0; s < FS; ++s) {
-    const R* o = part + ((size_t)b * FS + s) * 2 * per + r;
-    num += o[0];
-    den += o[per];
-  }
-  den = den < eps ? eps : den;
-  H[i] = H[i] * sqrt(num / den);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -537,14 +484,10 @@ __global__ void __launch_bounds__(BLK) fm_norm_src_kernel(R* __restrict__ W, R* 
   R* Wc = W + ((size_t)b * N + n) * F * K + k;  // Wc[f * K]
   R s = 0;
   for (int f = tid; f < F; f += BLK) s += Wc[(size_t)f * K];
-  s = wave_sum_down(s);
-  if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = s;
-  __syncthreads();
+  s = block_sum<R, BLK / WAVE>(s, red);
   if (tid == 0) {
-    R v = 0;
-    for (int w = 0; w < BLK / WAVE; ++w) v += red[w];
     const R eps = (R)eps_d;
-    tot = v < eps ? eps : v;
+    tot = s < eps ? eps : s;
   }
   __syncthreads();
   const R ws = tot;
@@ -620,30 +563,13 @@ template <typename Fn>
 int fm_dispatch(assx_ctx* ctx, int dtype, int M, Fn&& fn) {
   if (dtype != ASSX_F64 && dtype != ASSX_F32) return fail(ctx, ASSX_E_ARG, "bad dtype %d", dtype);
   auto go = [&](auto rt) -> int {
-    switch (M) {
-      case 2: return fn(rt, IntC<2>());
-      case 3: return fn(rt, IntC<3>());
-      case 4: return fn(rt, IntC<4>());
-      case 5: return fn(rt, IntC<5>());
-      case 6: return fn(rt, IntC<6>());
-      case 7: return fn(rt, IntC<7>());
-      case 8: return fn(rt, IntC<8>());
-    }
-    return fail(ctx, ASSX_E_UNSUPPORTED, "FastMNMF: n_channels must be in [2, 8], got %d", M);
+    return dispatch_channels(ctx, "FastMNMF", M, [&](auto mt) -> int { return fn(rt, mt); });
   };
   return dtype == ASSX_F64 ? go(double()) : go(float());
 }
 
 int fm_check(assx_ctx* ctx, int B, int M, int N, int F, int T, int K, int dtype) {
-  ASSX_REQUIRE_CTX(ctx);
-  ASSX_REQUIRE(ctx, B >= 1 && F >= 1 && T >= 1, ASSX_E_ARG, "invalid sizes B=%d F=%d T=%d", B, F, T);
-  ASSX_REQUIRE(ctx, dtype == ASSX_F64 || dtype == ASSX_F32, ASSX_E_ARG, "bad dtype %d", dtype);
-  ASSX_REQUIRE(ctx, M >= 2 && M <= 8, ASSX_E_UNSUPPORTED, "FastMNMF: n_channels must be in [2, 8], got %d", M);
-  ASSX_REQUIRE(ctx, N >= 1 && N <= NMAX, ASSX_E_UNSUPPORTED, "FastMNMF: n_sources must be in [1, 8], got %d", N);
-  ASSX_REQUIRE(ctx, K >= 1 && K <= KMAX, ASSX_E_UNSUPPORTED, "FastMNMF: n_basis must be in [1, 64], got %d", K);
-  ASSX_REQUIRE(ctx, (long long)M * F * T < (1LL << 28), ASSX_E_UNSUPPORTED,
-               "FastMNMF: one utterance must stay below 4 GiB in complex128 (M*F*T < 2^28)");
-  return 0;
+  return check_sizes(ctx, "FastMNMF", /*f64_only=*/false, B, M, N, F, T, K, dtype);
 }
 
 }  // namespace
@@ -706,9 +632,9 @@ int assx_fastmnmf_update_nmf(assx_ctx* ctx, void* W, void* H, const void* g, dou
                        (const R*)W, (const R*)H, (const R*)g, xt, part, eps, N, F, T, K, FS, nchunk);
     ASSX_LAUNCH_CHECK(ctx, "fm_act_partial_kernel");
     const size_t total = (size_t)B * NP * T;
-    hipLaunchKernelGGL((fm_act_apply_kernel<R>), dim3(nblocks(total, BLK)), dim3(BLK), 0, st, (R*)H, (const R*)part,
-                       eps, NP, T, FS, total);
-    ASSX_LAUNCH_CHECK(ctx, "fm_act_apply_kernel");
+    hipLaunchKernelGGL((act_apply_kernel<R>), dim3(nblocks(total, BLK)), dim3(BLK), 0, st, (R*)H, (const R*)part, eps,
+                       NP, T, FS, total);
+    ASSX_LAUNCH_CHECK(ctx, "act_apply_kernel");
     return 0;
   });
 }

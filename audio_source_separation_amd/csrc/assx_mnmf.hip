@@ -7,7 +7,7 @@
 // step re-forms X^ from the parameters as they stand:
 //
 //   basis       mn_eval_kernel<AB> -> a, b (B,N,F,T);  mn_basis_kernel    one workgroup per (b, f), reduce over t
-//   activation  mn_eval_kernel<AB>;  mn_act_partial_kernel (t block, f slice, b x k chunk);  mn_act_apply_kernel
+//   activation  mn_eval_kernel<AB>;  mn_act_partial_kernel (t block, f slice, b x k chunk);  act_apply_kernel
 //   latent      mn_eval_kernel<AB>;  mn_latent_partial_kernel per (b, f);  mn_latent_sum_kernel per (b, n, k) (one wave
 //               sums the bins in a fixed order);  mn_latent_apply_kernel per b (the update, then the normalisation over n)
 //   spatial     mn_spatial_partial_kernel (t slice, f, b): one wave recomputes P, y, lam for 64 frames at a time and
@@ -23,24 +23,18 @@
 // AGPRs; only the per-(f, n) Riccati kernels use scratch, from M = 6 on (profiles/mnmf_kernel_resource_usage.md).
 #include "assx_common.hpp"
 #include "assx_herm_linalg.hpp"
+#include "assx_mnmf_common.hpp"
 
 using namespace assx;
+using namespace assx::mf;
 using herm::Mat;
 
 namespace {
 
-constexpr int NMAX = 8;      // sources
-constexpr int KMAX = 64;     // n_basis
-constexpr int CH = 16;       // (numerator, denominator) pairs a thread accumulates per chunk
-constexpr int FS_ACT = 16;   // f slices of the activation reduction
 constexpr int EBLK = 128;    // threads (frames) of an evaluation workgroup
-constexpr int BLK = 256;     // threads of the per-bin reductions
-constexpr int ABLK = 64;     // threads (frames) of an activation workgroup
 constexpr int SP_SLICES = 8; // t slices of the spatial sums
 constexpr int MODE_AB = 1, MODE_LOSS = 2, MODE_SEP = 3;
 
-inline unsigned nblocks(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
-inline int act_slices(int F) { return F < FS_ACT ? F : FS_ACT; }
 inline int sp_slices(int T) {
   const int tiles = (T + WAVE - 1) / WAVE;
   return tiles < SP_SLICES ? tiles : SP_SLICES;
@@ -62,12 +56,6 @@ MnLayout mn_layout(int B, int M, int N, int F, int T, int K) {
   L.lpart = align_up(L.spp + (size_t)B * F * sp_slices(T) * N * 2 * M * M * d, 256);
   L.total = align_up(L.lpart + (size_t)B * F * nblocks(T, EBLK) * d, 256);
   return L;
-}
-
-__device__ __forceinline__ double wave_sum_down(double v) {  // fixed butterfly; the total lands in lane 0
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, WAVE);
-  return v;
 }
 
 // the bin's model in LDS: zt[n*K + k] = Z[n,k] Tb[f,k]; hr/hi[(n*M + i)*M + j] = H[f,n,i,j]
@@ -250,14 +238,8 @@ __global__ void __launch_bounds__(EBLK) mn_eval_kernel(const Cx<double>* __restr
     }
   }
   if constexpr (MODE == MODE_LOSS) {
-    term = wave_sum_down(term);
-    if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = term;
-    __syncthreads();
-    if (tid == 0) {
-      double s = 0.0;
-      for (int w = 0; w < EBLK / WAVE; ++w) s += red[w];
-      lpart[((size_t)b * F + f) * gridDim.x + blockIdx.x] = s;
-    }
+    const double s = block_sum<double, EBLK / WAVE>(term, red);
+    if (tid == 0) lpart[((size_t)b * F + f) * gridDim.x + blockIdx.x] = s;
   }
 }
 
@@ -268,14 +250,8 @@ __global__ void __launch_bounds__(BLK) mn_loss_finalize_kernel(const double* __r
   const int b = blockIdx.x, tid = threadIdx.x;
   double s = 0.0;
   for (int i = tid; i < n_per_b; i += BLK) s += lpart[(size_t)b * n_per_b + i];
-  s = wave_sum_down(s);
-  if ((tid & (WAVE - 1)) == 0) red[tid / WAVE] = s;
-  __syncthreads();
-  if (tid == 0) {
-    double ss = 0.0;
-    for (int w = 0; w < BLK / WAVE; ++w) ss += red[w];
-    loss[b] = ss;
-  }
+  s = block_sum<double, BLK / WAVE>(s, red);
+  if (tid == 0) loss[b] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -287,7 +263,7 @@ __global__ void __launch_bounds__(BLK) mn_basis_kernel(double* __restrict__ Tb, 
                                                        double eps, int B, int N, int F, int T, int K) {
   __shared__ double zs[NMAX * KMAX];
   __shared__ double red[BLK / WAVE][2 * CH];
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   for (int i = tid; i < N * K; i += BLK) zs[i] = Z[(size_t)b * N * K + i];
   __syncthreads();
   const size_t FT = (size_t)F * T, plane = (size_t)B * N * FT;
@@ -319,15 +295,9 @@ __global__ void __launch_bounds__(BLK) mn_basis_kernel(double* __restrict__ Tb, 
         }
       }
     }
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const double sn = wave_sum_down(num[c]), sd = wave_sum_down(den[c]);
-      if (lane == 0) red[w][2 * c] = sn, red[w][2 * c + 1] = sd;
-    }
-    __syncthreads();
+    double sn, sd;
+    block_pair_sums<double, BLK / WAVE>(num, den, red, sn, sd);
     if (tid < CH && k0 + tid < K) {
-      double sn = 0.0, sd = 0.0;
-      for (int q = 0; q < BLK / WAVE; ++q) sn += red[q][2 * tid], sd += red[q][2 * tid + 1];
       if (sd < eps) sd = eps;
       double* tp = Tb + ((size_t)b * F + f) * K + k0 + tid;
       *tp = *tp * sqrt(sn / sd);
@@ -388,21 +358,6 @@ __global__ void __launch_bounds__(ABLK) mn_act_partial_kernel(const double* __re
   }
 }
 
-__global__ void __launch_bounds__(BLK) mn_act_apply_kernel(double* __restrict__ V, const double* __restrict__ part,
-                                                           double eps, int K, int T, int FS, size_t total) {
-  const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
-  if (i >= total) return;
-  const size_t KT = (size_t)K * T, b = i / KT, r = i % KT;
-  double num = 0.0, den = 0.0;
-  for (int s = 0; s < FS; ++s) {
-    const size_t o = (b * FS + s) * 2 * KT + r;
-    num += part[o];
-    den += part[o + KT];
-  }
-  if (den < eps) den = eps;
-  V[i] = V[i] * sqrt(num / den);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // latent (mnmf.py:475-497): per (b, f) and pair (n, k): sum_t Tb[f,k] V[k,t] a_n (and b_n) into (B,F,2,N*K); then per b
 // the bins summed in ascending order, Z *= sqrt(num / den) (den < eps -> eps), Z /= sum_n Z (sum < eps -> eps).
@@ -412,7 +367,7 @@ __global__ void __launch_bounds__(BLK) mn_latent_partial_kernel(const double* __
                                                                 const double* __restrict__ ab, double* __restrict__ part,
                                                                 int B, int N, int F, int T, int K) {
   __shared__ double red[BLK / WAVE][2 * CH];
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const size_t FT = (size_t)F * T, plane = (size_t)B * N * FT;
   const double* tf = Tb + ((size_t)b * F + f) * K;
   const double* Vb = V + (size_t)b * K * T;
@@ -434,15 +389,9 @@ __global__ void __launch_bounds__(BLK) mn_latent_partial_kernel(const double* __
         }
       }
     }
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const double sn = wave_sum_down(num[c]), sd = wave_sum_down(den[c]);
-      if (lane == 0) red[w][2 * c] = sn, red[w][2 * c + 1] = sd;
-    }
-    __syncthreads();
+    double sn, sd;
+    block_pair_sums<double, BLK / WAVE>(num, den, red, sn, sd);
     if (tid < CH && p0 + tid < NP) {
-      double sn = 0.0, sd = 0.0;
-      for (int q = 0; q < BLK / WAVE; ++q) sn += red[q][2 * tid], sd += red[q][2 * tid + 1];
       const size_t o = ((size_t)b * F + f) * 2 * NP + p0 + tid;
       part[o] = sn;
       part[o + NP] = sd;
@@ -681,29 +630,11 @@ __global__ void __launch_bounds__(WAVE) mn_riccati_batch_kernel(const Cx<double>
 
 template <typename Fn>
 int mn_dispatch(assx_ctx* ctx, int M, Fn&& fn) {
-  switch (M) {
-    case 2: return fn(IntC<2>());
-    case 3: return fn(IntC<3>());
-    case 4: return fn(IntC<4>());
-    case 5: return fn(IntC<5>());
-    case 6: return fn(IntC<6>());
-    case 7: return fn(IntC<7>());
-    case 8: return fn(IntC<8>());
-  }
-  return fail(ctx, ASSX_E_UNSUPPORTED, "MNMF: n_channels must be in [2, 8], got %d", M);
+  return dispatch_channels(ctx, "MNMF", M, fn);
 }
 
 int mn_check(assx_ctx* ctx, int B, int M, int N, int F, int T, int K, int dtype) {
-  ASSX_REQUIRE_CTX(ctx);
-  ASSX_REQUIRE(ctx, B >= 1 && F >= 1 && T >= 1, ASSX_E_ARG, "invalid sizes B=%d F=%d T=%d", B, F, T);
-  ASSX_REQUIRE(ctx, dtype == ASSX_F64 || dtype == ASSX_F32, ASSX_E_ARG, "bad dtype %d", dtype);
-  ASSX_REQUIRE(ctx, dtype == ASSX_F64, ASSX_E_UNSUPPORTED, "MNMF: float64 only");
-  ASSX_REQUIRE(ctx, M >= 2 && M <= 8, ASSX_E_UNSUPPORTED, "MNMF: n_channels must be in [2, 8], got %d", M);
-  ASSX_REQUIRE(ctx, N >= 1 && N <= NMAX, ASSX_E_UNSUPPORTED, "MNMF: n_sources must be in [1, 8], got %d", N);
-  ASSX_REQUIRE(ctx, K >= 1 && K <= KMAX, ASSX_E_UNSUPPORTED, "MNMF: n_basis must be in [1, 64], got %d", K);
-  ASSX_REQUIRE(ctx, (long long)M * F * T < (1LL << 28), ASSX_E_UNSUPPORTED,
-               "MNMF: one utterance must stay below 4 GiB in complex128 (M*F*T < 2^28)");
-  return 0;
+  return check_sizes(ctx, "MNMF", /*f64_only=*/true, B, M, N, F, T, K, dtype);
 }
 
 #define MN_ARGS_OK(name) \
@@ -766,9 +697,9 @@ int assx_mnmf_update_activation(assx_ctx* ctx, const void* X, const void* Tb, vo
                      nchunk);
   ASSX_LAUNCH_CHECK(ctx, "mn_act_partial_kernel");
   const size_t total = (size_t)B * K * T;
-  hipLaunchKernelGGL(mn_act_apply_kernel, dim3(nblocks(total, BLK)), dim3(BLK), 0, st, (double*)V, (const double*)part,
-                     eps, K, T, FS, total);
-  ASSX_LAUNCH_CHECK(ctx, "mn_act_apply_kernel");
+  hipLaunchKernelGGL(act_apply_kernel<double>, dim3(nblocks(total, BLK)), dim3(BLK), 0, st, (double*)V,
+                     (const double*)part, eps, K, T, FS, total);
+  ASSX_LAUNCH_CHECK(ctx, "act_apply_kernel");
   return 0;
 }
 

@@ -224,6 +224,28 @@ def test_iterate_is_bit_identical_to_the_step_loop():
         assert np.array_equal(getattr(nl_slow, a), getattr(fast, a)), a
 
 
+def test_overridden_step_falls_back_to_the_step_loop():
+    """A subclass that overrides a step is run by the step loop (the override is called once per iteration), and ends
+    in the very bits of the one-call loop."""
+    calls = []
+
+    class Counting(cls()):
+        def update_SCM(self):
+            calls.append(len(self.loss))
+            super().update_SCM()
+
+    X, W0, H0 = _small()
+    plain, Yp = _run(X, W0, H0, 3)
+    model = Counting(n_basis=4, n_sources=2)
+    model.basis, model.activation = W0.copy(), H0.copy()
+    Y = model(X, iteration=3)
+    assert calls == [1, 2, 3]
+    assert np.array_equal(np.asarray(model.loss), np.asarray(plain.loss))
+    for a in ATTRS:
+        assert np.array_equal(getattr(model, a), getattr(plain, a)), a
+    assert np.array_equal(Y, Yp)
+
+
 def test_batch_is_bit_identical_to_single_calls_and_runs_repeat():
     Xs, Ws, Hs = [], [], []
     for b in range(3):

@@ -200,6 +200,37 @@ def test_bitwise_determinism_iterate_and_batch():
         assert np.array_equal(mb.spatial[i], singles[i][2])
 
 
+def test_overridden_step_falls_back_to_the_step_loop():
+    """A subclass that overrides a step is run by the step loop (the override is called once per iteration), and ends
+    in the very bits of the one-call loop.  T = 70 leaves one ragged 64-frame tile."""
+    M, N, K, F, T = 3, 2, 4, 5, 70
+    rng = np.random.default_rng(12)
+    X = rng.standard_normal((M, F, T)) + 1j * rng.standard_normal((M, F, T))
+    Z0 = rng.random((N, K)) * 1e-2 + 1 / N
+    Z0 /= Z0.sum(axis=0)
+    T0, V0 = rng.random((F, K)), rng.random((K, T))
+    calls = []
+
+    class Counting(cls()):
+        def update_latent_sawada(self):
+            calls.append(len(self.loss))
+            super().update_latent_sawada()
+
+    def run(C):
+        m = C(n_basis=K, n_sources=N)
+        m.latent, m.basis, m.activation = Z0.copy(), T0.copy(), V0.copy()
+        return m, m(X, iteration=3)
+
+    plain, Yp = run(cls())
+    assert calls == []
+    model, Y = run(Counting)
+    assert calls == [1, 2, 3]
+    assert np.array_equal(np.asarray(model.loss), np.asarray(plain.loss)) and len(model.loss) == 4
+    for a in ATTRS:
+        assert np.array_equal(getattr(model, a), getattr(plain, a)), a
+    assert np.array_equal(Y, Yp) and np.array_equal(model.estimation, plain.estimation)
+
+
 def _fullsize(M, N, K, F, T, n_iter, seed):
     rng = np.random.default_rng(seed)
     X = rng.standard_normal((M, F, T)) + 1j * rng.standard_normal((M, F, T))

@@ -34,7 +34,8 @@ def main():
                          g("group_segment_fixed_size")))
     print(f"{'vgpr':>5} {'sgpr':>5} {'spill':>5} {'scratch':>7} {'lds':>6}  kernel")
     for name, v, s, sp, ps, lds in rows:
-        short = re.sub(r"^void ", "", name)
+        # drop the anonymous-namespace qualifier first: its parenthesis is not the start of the parameter list
+        short = re.sub(r"^void ", "", name).replace("(anonymous namespace)::", "")
         short = re.sub(r"\(.*$", "", short)
         print(f"{v:>5} {s:>5} {sp:>5} {ps:>7} {lds:>6}  {short}")
 
