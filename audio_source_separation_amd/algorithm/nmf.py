@@ -4,6 +4,9 @@ of the reference (/root/reference/src/algorithm/nmf.py:10-56, 150-600).
 Same constructors, `nmf(target, iteration=100, **kwargs) -> (basis.copy(), activation.copy())`,
 `basis` / `activation` / `loss` attributes.  `update_once()` and the per-iteration loss run as HIP
 kernels (include/assx.h: assx_nmf_update / assx_nmf_loss); there is no CPU fallback.
+
+`ComplexEUCNMF` (nmf.py:58-114, 597-676) returns `(basis.copy(), activation.copy(), phase.copy())` and runs on
+assx_cnmf_update / assx_cnmf_iterate.
 """
 import numpy as np
 
@@ -291,3 +294,171 @@ class CauchyNMF(NMFbase):
         NMFbase.update_once(self)
 
     update_once_naive = update_once_mm = update_once_me = update_once_mm_fast = _update_once_checked
+
+
+class ComplexNMFbase(DeviceState):
+    """reference: nmf.py:58-114.  `phase` holds the angles (n_bins, n_basis, n_frames), as in the reference."""
+    basis = DeviceArray("T", complex_=False)
+    activation = DeviceArray("V", complex_=False)
+    phase = DeviceArray("Phi", complex_=False)
+
+    N_BASIS_MAX = 64
+
+    def __init__(self, n_basis=2, regularizer=0.1, eps=EPS, *, dtype='float64', device=None, recordable_loss=True):
+        """
+        Args:
+            n_basis: number of basis
+            recordable_loss: extension: False skips the criterion, `loss` then stays empty.
+        """
+        if str(dtype) not in ('float64', 'double', 'complex128'):
+            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+
+        self.n_basis = n_basis
+        self.regularizer = regularizer
+        self.loss = LazyLossList()
+        self.recordable_loss = recordable_loss
+
+        self.eps = eps
+
+        self.dtype = 'float64'
+        self.device = device
+        self._engine = None
+
+    def __call__(self, target, iteration=100, **kwargs):
+        self.target = target
+
+        self._reset(**kwargs)
+
+        self.update(iteration=iteration)
+
+        T, V = self.basis, self.activation
+        Phi = self.phase
+
+        return T.copy(), V.copy(), Phi.copy()
+
+    def _reset(self, **kwargs):
+        assert self.target is not None, "Specify data!"
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+        n_basis = self.n_basis
+        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
+            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        target = self.target
+        ndim = target.dim() if isinstance(target, torch.Tensor) else np.ndim(target)
+        if ndim not in (2, 3):
+            raise ValueError("target must be (n_bins, n_frames), got {} dims".format(ndim))
+
+        eng = self._ensure_engine()
+        self._batched = ndim == 3
+        Xd = to_device(target, eng.prec.cplx, eng.dev)
+        if not self._batched:
+            Xd = Xd.unsqueeze(0)
+        self._X = Xd.contiguous()
+        B, n_bins, n_frames = (int(s) for s in self._X.shape)
+        self._ws = eng.cnmf_workspace(B, n_bins, n_frames, n_basis)
+
+        # no warm start: three draws from the global RNG, in the reference's order (nmf.py:92-94)
+        lead = (B,) if self._batched else ()
+        self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
+        self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
+        self.phase = 2 * np.pi * np.random.rand(*(lead + (n_bins, n_basis, n_frames)))
+
+    def init_phase(self):
+        """nmf.py:96-101: every basis starts from the target's phase.  A NumPy target is handled on the host, like the
+        reference's; a device tensor stays on the device."""
+        n_basis = self.n_basis
+        target = self.target
+
+        if isinstance(target, torch.Tensor):
+            phase = torch.angle(self._X)
+            self._set_dev("Phi", phase.unsqueeze(2).expand(-1, -1, n_basis, -1).contiguous())
+        else:
+            phase = np.angle(target)
+            self.phase = np.tile(phase[..., np.newaxis, :], reps=(1,) * (phase.ndim - 1) + (n_basis, 1))
+
+    def _model(self):
+        return self._dev("T", False), self._dev("V", False), self._dev("Phi", False)
+
+    def reconstruct(self):
+        """Extension: sum_k basis * activation * exp(1j * phase), (n_bins, n_frames) complex -- what the reference's
+        users form next (egs/nmf-example/cnmf)."""
+        Y = to_numpy(self._engine.cnmf_reconstruct(*self._model()), np.complex128)
+        return Y if self._batched else Y[0]
+
+    def update(self, iteration=100):
+        for idx in range(iteration):
+            self.update_once()
+
+            if self.recordable_loss:
+                self._record_loss()
+
+    def update_once(self):
+        raise NotImplementedError("Implement 'update_once' method")
+
+
+class ComplexEUCNMF(ComplexNMFbase):
+    """reference: nmf.py:597-676 (Kameoka's complex NMF).  float64, 1 <= n_basis <= 64.  `Beta` is derived from `basis`
+    and `activation` whenever it is read or used (the reference stores it and recomputes it after every update).  The
+    recorded loss is sum |sum_k T V exp(i Phi) - X|^2; the reference's own list multiplies by the angle Phi itself
+    (nmf.py:620), see DESIGN.md section 11."""
+
+    def __init__(self, n_basis=2, regularizer=0.1, p=1, eps=EPS, *, dtype='float64', device=None, recordable_loss=True):
+        """
+        Args:
+            n_basis: number of basis
+        """
+        super().__init__(n_basis=n_basis, eps=eps, dtype=dtype, device=device, recordable_loss=recordable_loss)
+
+        self.regularizer, self.p = regularizer, p
+
+    def _reset(self, **kwargs):
+        super()._reset(**kwargs)
+
+        self.init_phase()
+        self.update_beta()
+
+    @property
+    def Beta(self):
+        B = to_numpy(self._engine.cnmf_beta(self._dev("T", False), self._dev("V", False), eps=self.eps), np.float64)
+        return B if self._batched else B[0]
+
+    def update_beta(self):
+        """nmf.py:669-676.  Nothing to do: Beta is a function of basis and activation, formed where it is used."""
+
+    def _fast_loop_ok(self):
+        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_cnmf_iterate when every step is this module's."""
+        cls = type(self)
+        return all(getattr(cls, n) is getattr(ComplexEUCNMF, n) for n in ("update", "update_once", "update_beta",
+                                                                           "_record_loss")) \
+            and isinstance(self.loss, LazyLossList)
+
+    def _record_loss(self):
+        T, V, Phi = self._model()
+        loss = self._engine.cnmf_loss(self._X, T, V, Phi, self._ws, eps=self.eps)
+        if isinstance(self.loss, LazyLossList):
+            self.loss.append_device(loss, self._batched)
+        else:
+            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+
+    def update(self, iteration=100):
+        if iteration > 0 and self._fast_loop_ok():
+            eng = self._engine
+            loss = eng.empty((iteration, int(self._X.shape[0])), dtype=torch.float64) if self.recordable_loss else None
+            T, V, Phi = self._model()
+            eng.cnmf_iterate(iteration, self._X, T, V, Phi, self._ws, regularizer=self.regularizer, p=self.p,
+                             eps=self.eps, loss=loss)
+            self._touch("T", "V", "Phi")
+            if loss is not None:
+                self.loss.append_device_block(loss, self._batched)
+            return
+
+        super().update(iteration=iteration)
+
+    def update_once(self):
+        T, V, Phi = self._model()
+        self._engine.cnmf_update(self._X, T, V, Phi, self._ws, regularizer=self.regularizer, p=self.p, eps=self.eps)
+        self._touch("T", "V", "Phi")
+
+        self.update_beta()

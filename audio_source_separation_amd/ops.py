@@ -552,6 +552,84 @@ class Engine:
                                               ptr(Z), ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), B, M, N, F,
                                               T, K, _lib.F64, self._st()), "assx_mnmf_iterate")
 
+    # ------------------------------------------------------------------ ComplexEUCNMF (algorithm/nmf.py)
+    def _cnmf_dims(self, Tb, V, Phi=None, X=None, ws=None):
+        """Sizes of a complex-NMF call, with every array checked against them (the kernels take pointers and sizes: an
+        array of another shape would be read past its end).  Refused with ValueError before any launch."""
+        if self.prec.code != _lib.F64:
+            raise ValueError("ComplexEUCNMF supports float64 only")
+        if Tb.dim() != 3 or V.dim() != 3:
+            raise ValueError("ComplexEUCNMF: expected basis (B,F,K) and activation (B,K,T), got %s and %s"
+                             % (tuple(Tb.shape), tuple(V.shape)))
+        B, F, K = (int(d) for d in Tb.shape)
+        T = int(V.shape[2])
+        if not 1 <= K <= 64:
+            raise ValueError("ComplexEUCNMF: n_basis must be in [1, 64], got %d" % K)
+        want = {"basis": (Tb, (B, F, K), torch.float64), "activation": (V, (B, K, T), torch.float64)}
+        if Phi is not None:
+            want["phase"] = (Phi, (B, F, K, T), torch.float64)
+        if X is not None:
+            want["target"] = (X, (B, F, T), torch.complex128)
+        for name, (a, shape, dt) in want.items():
+            if a.dtype != dt or a.device != self.dev:
+                raise ValueError("ComplexEUCNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
+            if tuple(a.shape) != shape or not a.is_contiguous():
+                raise ValueError("ComplexEUCNMF: %s has shape %s, but the basis %s needs %s (contiguous)"
+                                 % (name, tuple(a.shape), (B, F, K), shape))
+        if ws is not None:
+            need = self._L.assx_cnmf_workspace_bytes(B, F, T, K, _lib.F64)
+            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
+                raise ValueError("ComplexEUCNMF: workspace of %d bytes, %d needed for B=%d F=%d T=%d K=%d"
+                                 % (ws.numel(), need, B, F, T, K))
+        return B, F, T, K
+
+    def cnmf_workspace(self, B, F, T, K):
+        n = self._L.assx_cnmf_workspace_bytes(B, F, T, K, self.prec.code)
+        if n == 0:
+            raise ValueError("ComplexEUCNMF supports float64 and 1 <= n_basis <= 64; got dtype=%s, n_basis=%d"
+                             % (self.prec.name, K))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def cnmf_update(self, X, Tb, V, Phi, ws, regularizer=0.1, p=1, eps=1e-12):
+        B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
+        self._check(self._L.assx_cnmf_update(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Phi), float(regularizer), float(p),
+                                             float(eps), ptr(ws), B, F, T, K, _lib.F64, self._st()), "assx_cnmf_update")
+
+    def cnmf_loss(self, X, Tb, V, Phi, ws, eps=1e-12, loss=None):
+        """loss (B,) float64: sum |sum_k T V e^{i Phi} - X|^2 of the model as it stands."""
+        B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
+        loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
+        self._fastmnmf_need(loss, B, "loss")
+        self._check(self._L.assx_cnmf_loss(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Phi), float(eps), ptr(loss), ptr(ws), B,
+                                           F, T, K, _lib.F64, self._st()), "assx_cnmf_loss")
+        return loss
+
+    def cnmf_beta(self, Tb, V, eps=1e-12, out=None):
+        """(B,F,K,T): T V / max(sum_k T V, eps)."""
+        B, F, T, K = self._cnmf_dims(Tb, V)
+        Beta = out if out is not None else self.empty((B, F, K, T), dtype=torch.float64)
+        self._fastmnmf_need(Beta, B * F * K * T, "out")
+        self._check(self._L.assx_cnmf_beta(self.ctx, ptr(Tb), ptr(V), float(eps), ptr(Beta), B, F, T, K, _lib.F64,
+                                           self._st()), "assx_cnmf_beta")
+        return Beta
+
+    def cnmf_reconstruct(self, Tb, V, Phi, out=None):
+        """(B,F,T) complex: sum_k T V e^{i Phi}."""
+        B, F, T, K = self._cnmf_dims(Tb, V, Phi)
+        Y = out if out is not None else self.empty((B, F, T), dtype=torch.complex128)
+        self._fastmnmf_need(Y, B * F * T, "out")
+        self._check(self._L.assx_cnmf_reconstruct(self.ctx, ptr(Tb), ptr(V), ptr(Phi), ptr(Y), B, F, T, K, _lib.F64,
+                                                  self._st()), "assx_cnmf_reconstruct")
+        return Y
+
+    def cnmf_iterate(self, n_iter, X, Tb, V, Phi, ws, regularizer=0.1, p=1, eps=1e-12, loss=None):
+        """n_iter x update; loss: (n_iter, B) float64 or None."""
+        B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
+        self._fastmnmf_need(loss, int(n_iter) * B, "loss")
+        self._check(self._L.assx_cnmf_iterate(self.ctx, int(n_iter), ptr(X), ptr(Tb), ptr(V), ptr(Phi),
+                                              float(regularizer), float(p), float(eps), ptr(loss), ptr(ws), B, F, T, K,
+                                              _lib.F64, self._st()), "assx_cnmf_iterate")
+
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""
         if A.dim() != 3 or tuple(Bm.shape) != tuple(A.shape) or A.shape[1] != A.shape[2]:

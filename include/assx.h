@@ -372,6 +372,41 @@ int assx_mnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* X, v
 int assx_hermitian_riccati(assx_ctx* ctx, const void* A, const void* Bm, void* H, int32_t* status, int n, int M,
                            int dtype, void* stream);
 
+/* ---- (f7) ComplexEUCNMF, Kameoka's complex NMF (src/algorithm/nmf.py:58-114, 597-676) ---------------------------------
+ * State (float64 only): X (B,F,T) complex, Tb (B,F,K) real = basis, V (B,K,T) real = activation, Phi (B,F,K,T) real =
+ * phase angles, frames innermost.  The reference's Beta is a function of Tb and V -- Tb V / max(sum_k Tb V, eps),
+ * recomputed at the end of every update (nmf.py:669-676) -- and is never stored here.  1 <= K <= 64 and F, T >= 1
+ * (ASSX_E_ARG outside), dtype ASSX_F64 (ASSX_F32: ASSX_E_UNSUPPORTED).  `ws` (assx_cnmf_workspace_bytes; 0 for an empty
+ * or unsupported problem, no GPU needed) is scratch.  No float atomics and no partition that depends on B: results are
+ * bit-reproducible and a batch equals its single-utterance calls bit for bit.
+ *   assx_cnmf_update       one update_once (nmf.py:624-667), in place: Beta floored at eps, ZX = X - sum_k Tb V e^{i Phi},
+ *                          Zbar = Tb V e^{i Phi} + Beta ZX, V floored at eps from here on, Re = real(conj(Zbar) e^{i Phi}),
+ *                          Tb' = sum_t (V / Beta) Re / max(sum_t V^2 / Beta, eps),
+ *                          V' = sum_f (Tb' / Beta) Re / max(sum_f Tb'^2 / Beta + regularizer p V^(p-2), eps),
+ *                          Phi' = angle(Zbar) (0 where Zbar = 0), Tb'' = Tb' / sum_f Tb' (no floor, as in the reference).
+ *                          p = 1 and p = 2 skip the power.  Tb and V may go negative, as in the reference.
+ *   assx_cnmf_loss         loss (B,) float64 = sum_{f,t} |sum_k Tb V e^{i Phi} - X|^2 of the model as it stands.
+ *   assx_cnmf_beta         Beta (B,F,K,T) = Tb V / max(sum_k Tb V, eps) (update_beta; not floored: nmf.py:632 floors it
+ *                          at the start of the next update).
+ *   assx_cnmf_reconstruct  Y (B,F,T) complex = sum_k Tb V e^{i Phi}.
+ *   assx_cnmf_iterate      n_iter x assx_cnmf_update, enqueued without a synchronisation; the model is bit for bit that
+ *                          of n_iter calls of assx_cnmf_update.  loss: (n_iter, B) float64 or NULL; loss[i] is the loss
+ *                          of the model after update i + 1.  It is the sum of |ZX|^2 that update i + 2 forms anyway, by
+ *                          the kernel and in the order assx_cnmf_loss uses, so loss[i] equals assx_cnmf_loss of that model
+ *                          BIT FOR BIT; only the last entry costs a pass of its own. */
+size_t assx_cnmf_workspace_bytes(int B, int F, int T, int K, int dtype);
+int assx_cnmf_update(assx_ctx* ctx, const void* X, void* Tb, void* V, void* Phi, double regularizer, double p,
+                     double eps, void* ws, int B, int F, int T, int K, int dtype, void* stream);
+int assx_cnmf_loss(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const void* Phi, double eps,
+                   double* loss /* (B,) */, void* ws, int B, int F, int T, int K, int dtype, void* stream);
+int assx_cnmf_beta(assx_ctx* ctx, const void* Tb, const void* V, double eps, void* Beta, int B, int F, int T, int K,
+                   int dtype, void* stream);
+int assx_cnmf_reconstruct(assx_ctx* ctx, const void* Tb, const void* V, const void* Phi, void* Y, int B, int F, int T,
+                          int K, int dtype, void* stream);
+int assx_cnmf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* Tb, void* V, void* Phi, double regularizer,
+                      double p, double eps, double* loss /* (n_iter,B) or NULL */, void* ws, int B, int F, int T, int K,
+                      int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
