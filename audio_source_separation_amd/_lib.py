@@ -87,6 +87,11 @@ SIGNATURES = {
     "assx_cnmf_beta": (_i, [_vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_cnmf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_cnmf_iterate": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_ntf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "assx_ntf_update": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ntf_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ntf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ntf_iterate": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

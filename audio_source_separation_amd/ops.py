@@ -630,6 +630,80 @@ class Engine:
                                               float(regularizer), float(p), float(eps), ptr(loss), ptr(ws), B, F, T, K,
                                               _lib.F64, self._st()), "assx_cnmf_iterate")
 
+    # ------------------------------------------------------------------ EUCNTF (algorithm/ntf.py)
+    def _ntf_dims(self, Z, Tb, V, X=None, ws=None):
+        """Sizes of an NTF call, with every array checked against them (the kernels take pointers and sizes: an array of
+        another shape would be read past its end).  Refused with ValueError before any launch."""
+        if self.prec.code != _lib.F64:
+            raise ValueError("EUCNTF supports float64 only")
+        if Z.dim() != 3 or Tb.dim() != 3 or V.dim() != 3:
+            raise ValueError("EUCNTF: expected partitioning (B,N,K), basis (B,I,K) and activation (B,K,J), got %s, %s "
+                             "and %s" % (tuple(Z.shape), tuple(Tb.shape), tuple(V.shape)))
+        B, N, K = (int(d) for d in Z.shape)
+        I, J = int(Tb.shape[1]), int(V.shape[2])
+        if not 1 <= K <= 64:
+            raise ValueError("EUCNTF: n_basis must be in [1, 64], got %d" % K)
+        if not 1 <= N <= 32:
+            raise ValueError("EUCNTF: n_channels must be in [1, 32], got %d" % N)
+        want = {"partitioning": (Z, (B, N, K)), "basis": (Tb, (B, I, K)), "activation": (V, (B, K, J))}
+        if X is not None:
+            want["target"] = (X, (B, N, I, J))
+        for name, (a, shape) in want.items():
+            self._ntf_array(a, shape, name)
+        if ws is not None:
+            need = self._L.assx_ntf_workspace_bytes(B, N, I, J, K, _lib.F64)
+            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
+                raise ValueError("EUCNTF: workspace of %d bytes, %d needed for B=%d N=%d I=%d J=%d K=%d"
+                                 % (ws.numel(), need, B, N, I, J, K))
+        return B, N, I, J, K
+
+    def _ntf_array(self, a, shape, name):
+        if a.dtype != torch.float64 or a.device != self.dev:
+            raise ValueError("EUCNTF: %s must be torch.float64 on %s, got %s on %s" % (name, self.dev, a.dtype, a.device))
+        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
+            raise ValueError("EUCNTF: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
+
+    def ntf_workspace(self, B, N, I, J, K):
+        n = self._L.assx_ntf_workspace_bytes(B, N, I, J, K, self.prec.code)
+        if n == 0:
+            raise ValueError("EUCNTF supports float64, 1 <= n_basis <= 64 and 1 <= n_channels <= 32; got dtype=%s, "
+                             "n_basis=%d, n_channels=%d" % (self.prec.name, K, N))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def ntf_update(self, X, Z, Tb, V, ws, eps=1e-12):
+        """One update_once of (Z, Tb, V), in place."""
+        B, N, I, J, K = self._ntf_dims(Z, Tb, V, X, ws)
+        self._check(self._L.assx_ntf_update(self.ctx, ptr(X), ptr(Z), ptr(Tb), ptr(V), float(eps), ptr(ws), B, N, I, J, K,
+                                            _lib.F64, self._st()), "assx_ntf_update")
+
+    def ntf_loss(self, X, Z, Tb, V, ws, loss=None):
+        """loss (B,) float64: sum (X - sum_k Z T V)^2 of the model as it stands."""
+        B, N, I, J, K = self._ntf_dims(Z, Tb, V, X, ws)
+        loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
+        self._ntf_array(loss, (B,), "loss")
+        self._check(self._L.assx_ntf_loss(self.ctx, ptr(X), ptr(Z), ptr(Tb), ptr(V), ptr(loss), ptr(ws), B, N, I, J, K,
+                                          _lib.F64, self._st()), "assx_ntf_loss")
+        return loss
+
+    def ntf_reconstruct(self, Z, Tb, V, out=None):
+        """(B,N,I,J): sum_k Z T V."""
+        B, N, I, J, K = self._ntf_dims(Z, Tb, V)
+        Xh = out if out is not None else self.empty((B, N, I, J), dtype=torch.float64)
+        self._ntf_array(Xh, (B, N, I, J), "out")
+        self._check(self._L.assx_ntf_reconstruct(self.ctx, ptr(Z), ptr(Tb), ptr(V), ptr(Xh), B, N, I, J, K, _lib.F64,
+                                                 self._st()), "assx_ntf_reconstruct")
+        return Xh
+
+    def ntf_iterate(self, n_iter, X, Z, Tb, V, ws, eps=1e-12, loss=None):
+        """n_iter x update; loss: (n_iter, B) float64 or None."""
+        B, N, I, J, K = self._ntf_dims(Z, Tb, V, X, ws)
+        if int(n_iter) < 0:
+            raise ValueError("EUCNTF: n_iter must be >= 0, got %d" % int(n_iter))
+        if loss is not None:
+            self._ntf_array(loss, (int(n_iter), B), "loss")
+        self._check(self._L.assx_ntf_iterate(self.ctx, int(n_iter), ptr(X), ptr(Z), ptr(Tb), ptr(V), float(eps),
+                                             ptr(loss), ptr(ws), B, N, I, J, K, _lib.F64, self._st()), "assx_ntf_iterate")
+
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""
         if A.dim() != 3 or tuple(Bm.shape) != tuple(A.shape) or A.shape[1] != A.shape[2]:

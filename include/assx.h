@@ -407,6 +407,35 @@ int assx_cnmf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* Tb, void* 
                       double p, double eps, double* loss /* (n_iter,B) or NULL */, void* ws, int B, int F, int T, int K,
                       int dtype, void* stream);
 
+/* ---- (f8) EUCNTF, non-negative tensor factorisation (src/algorithm/ntf.py:50-102) -----------------------------------------
+ * Model X[n,i,j] ~ Xh[n,i,j] = sum_k Z[n,k] Tb[i,k] V[k,j].  State (float64 only, frames innermost): X (B,N,I,J) target,
+ * Z (B,N,K) partitioning, Tb (B,I,K) basis, V (B,K,J) activation.  1 <= K <= 64, 1 <= N <= 32 and B, I, J >= 1
+ * (ASSX_E_ARG outside), dtype ASSX_F64 (ASSX_F32: ASSX_E_UNSUPPORTED).  `ws` (assx_ntf_workspace_bytes; 0 for an empty or
+ * unsupported problem, no GPU needed) is scratch; it never holds a reconstruction of X.  No float atomics and no partition
+ * that depends on B: results are bit-reproducible and a batch equals its single calls bit for bit.
+ *   assx_ntf_update       one update_once (ntf.py:57-93), in place, fl(a) = max(a, eps) on numerator AND denominator:
+ *                           Tb' = Tb o fl(sum_{n,j} X Z V)    / fl(Tb  ((Z^T Z)    o (V V^T)))
+ *                           V'  = V  o fl(sum_{n,i} X Z Tb')  / fl(((Z^T Z)   o (Tb'^T Tb')) V)
+ *                           Z'  = Z  o fl(sum_{i,j} X Tb' V') / fl(Z  ((Tb'^T Tb') o (V' V'^T)))
+ *                         The denominators are the reference's sums over Xh (which is not floored) in Gram form.
+ *   assx_ntf_loss         loss (B,) float64 = sum (X - Xh)^2 of the model as it stands, the difference formed per entry.
+ *   assx_ntf_reconstruct  Xh (B,N,I,J).
+ *   assx_ntf_iterate      n_iter x assx_ntf_update, enqueued without a synchronisation; the model is bit for bit that of
+ *                         n_iter calls of assx_ntf_update.  loss: (n_iter, B) float64 or NULL; loss[i] is the loss of the
+ *                         model after update i + 1, formed while update i + 2 reads X for the basis, by the code and in
+ *                         the order of assx_ntf_loss: loss[i] equals assx_ntf_loss of that model BIT FOR BIT; only the last
+ *                         entry costs a pass of its own. */
+size_t assx_ntf_workspace_bytes(int B, int N, int I, int J, int K, int dtype);
+int assx_ntf_update(assx_ctx* ctx, const void* X, void* Z, void* Tb, void* V, double eps, void* ws, int B, int N, int I,
+                    int J, int K, int dtype, void* stream);
+int assx_ntf_loss(assx_ctx* ctx, const void* X, const void* Z, const void* Tb, const void* V, double* loss /* (B,) */,
+                  void* ws, int B, int N, int I, int J, int K, int dtype, void* stream);
+int assx_ntf_reconstruct(assx_ctx* ctx, const void* Z, const void* Tb, const void* V, void* Xh, int B, int N, int I, int J,
+                         int K, int dtype, void* stream);
+int assx_ntf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* Z, void* Tb, void* V, double eps,
+                     double* loss /* (n_iter,B) or NULL */, void* ws, int B, int N, int I, int J, int K, int dtype,
+                     void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
