@@ -20,7 +20,7 @@ W_NONE, W_NT, W_NFT = 0, 1, 2
 IVA_LAPLACE, IVA_GAUSS = 0, 1
 NMF_EUC, NMF_KL, NMF_IS_MM, NMF_IS_ME = 0, 1, 2, 3
 NMF_T, NMF_CAUCHY_NAIVE, NMF_CAUCHY_MM, NMF_CAUCHY_ME, NMF_CAUCHY_MM_FAST = 4, 5, 6, 7, 8
-STATUS_SINGULAR, STATUS_COND_REJECT = 1, 2
+STATUS_SINGULAR, STATUS_COND_REJECT, STATUS_NOT_CONVERGED = 1, 2, 4
 SPATIAL_IP, SPATIAL_ISS, SPATIAL_IP2 = 0, 1, 2
 
 _vp = ctypes.c_void_p
@@ -92,6 +92,15 @@ SIGNATURES = {
     "assx_ntf_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_ntf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_ntf_iterate": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "assx_psdtf_to_psd": (_i, [_vp, _vp, _i, _i, _d, _vp]),
+    "assx_psdtf_update_basis": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_update_activation": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_normalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_update": (_i, [_vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_loss": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_psdtf_iterate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

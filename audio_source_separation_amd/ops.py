@@ -704,6 +704,109 @@ class Engine:
         self._check(self._L.assx_ntf_iterate(self.ctx, int(n_iter), ptr(X), ptr(Z), ptr(Tb), ptr(V), float(eps),
                                              ptr(loss), ptr(ws), B, N, I, J, K, _lib.F64, self._st()), "assx_ntf_iterate")
 
+    # ------------------------------------------------------------------ LDPSDTF (algorithm/psdtf.py)
+    def _psdtf_dims(self, V, H, X=None, ws=None, status=None):
+        """Sizes of a PSDTF call, with every array checked against them (the kernels take pointers and sizes: an array of
+        another shape would be read past its end).  Refused with ValueError before any launch."""
+        if self.prec.code != _lib.F64:
+            raise ValueError("LDPSDTF supports float64 only")
+        if V.dim() != 4 or H.dim() != 3 or V.shape[2] != V.shape[3]:
+            raise ValueError("LDPSDTF: expected basis (B,K,M,M) and activation (B,K,T), got %s and %s"
+                             % (tuple(V.shape), tuple(H.shape)))
+        B, K, M = (int(d) for d in V.shape[:3])
+        T = int(H.shape[2])
+        if not 1 <= K <= 64:
+            raise ValueError("LDPSDTF: n_basis must be in [1, 64], got %d" % K)
+        if not 1 <= M <= 64:
+            raise ValueError("LDPSDTF: n_bins must be in [1, 64], got %d" % M)
+        if B < 1 or T < 1:
+            raise ValueError("LDPSDTF: empty problem B=%d T=%d" % (B, T))
+        want = {"basis": (V, (B, K, M, M)), "activation": (H, (B, K, T))}
+        if X is not None:
+            want["target"] = (X, (B, T, M, M))
+        for name, (a, shape) in want.items():
+            self._psdtf_array(a, shape, name)
+        if ws is not None:
+            need = self._L.assx_psdtf_workspace_bytes(B, M, T, K, _lib.F64)
+            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
+                raise ValueError("LDPSDTF: workspace of %d bytes, %d needed for B=%d M=%d T=%d K=%d"
+                                 % (ws.numel(), need, B, M, T, K))
+        if status is not None:
+            self._psdtf_array(status, (B,), "status", torch.int32)
+        return B, M, T, K
+
+    def _psdtf_array(self, a, shape, name, dtype=torch.float64):
+        if a.dtype != dtype or a.device != self.dev:
+            raise ValueError("LDPSDTF: %s must be %s on %s, got %s on %s" % (name, dtype, self.dev, a.dtype, a.device))
+        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
+            raise ValueError("LDPSDTF: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
+
+    def psdtf_workspace(self, B, M, T, K):
+        n = self._L.assx_psdtf_workspace_bytes(B, M, T, K, self.prec.code)
+        if n == 0:
+            raise ValueError("LDPSDTF supports float64, 1 <= n_bins <= 64 and 1 <= n_basis <= 64; got dtype=%s, "
+                             "n_bins=%d, n_basis=%d" % (self.prec.name, M, K))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def psdtf_to_psd(self, A, eps=1e-12):
+        """to_PSD of (n, M, M) symmetric matrices, in place."""
+        if A.dim() != 3 or A.shape[1] != A.shape[2] or not 1 <= int(A.shape[1]) <= 64 or int(A.shape[0]) < 1:
+            raise ValueError("psdtf_to_psd: expected (n, M, M) with 1 <= M <= 64, got %s" % (tuple(A.shape),))
+        self._psdtf_array(A, tuple(A.shape), "A")
+        self._check(self._L.assx_psdtf_to_psd(self.ctx, ptr(A), int(A.shape[0]), int(A.shape[1]), float(eps), self._st()),
+                    "assx_psdtf_to_psd")
+        return A
+
+    def psdtf_update_basis(self, X, V, H, ws, eps=1e-12, status=None):
+        B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
+        self._check(self._L.assx_psdtf_update_basis(self.ctx, ptr(X), ptr(V), ptr(H), float(eps), ptr(status), ptr(ws), B, M,
+                                                    T, K, _lib.F64, self._st()), "assx_psdtf_update_basis")
+
+    def psdtf_update_activation(self, X, V, H, eps=1e-12, status=None):
+        B, M, T, K = self._psdtf_dims(V, H, X, None, status)
+        self._check(self._L.assx_psdtf_update_activation(self.ctx, ptr(X), ptr(V), ptr(H), float(eps), ptr(status), B, M, T,
+                                                         K, _lib.F64, self._st()), "assx_psdtf_update_activation")
+
+    def psdtf_normalize(self, V, H):
+        B, M, T, K = self._psdtf_dims(V, H)
+        self._check(self._L.assx_psdtf_normalize(self.ctx, ptr(V), ptr(H), B, M, T, K, _lib.F64, self._st()),
+                    "assx_psdtf_normalize")
+
+    def psdtf_update(self, X, V, H, ws, eps=1e-12, normalize=True, status=None):
+        """One update_once of (V, H), in place."""
+        B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
+        self._check(self._L.assx_psdtf_update(self.ctx, ptr(X), ptr(V), ptr(H), float(eps), int(bool(normalize)),
+                                              ptr(status), ptr(ws), B, M, T, K, _lib.F64, self._st()), "assx_psdtf_update")
+
+    def psdtf_loss(self, X, V, H, ws, eps=1e-12, loss=None, status=None):
+        """loss (B,) float64: the log-det divergence of the model as it stands, summed over the frames."""
+        B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
+        loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
+        self._psdtf_array(loss, (B,), "loss")
+        self._check(self._L.assx_psdtf_loss(self.ctx, ptr(X), ptr(V), ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), B,
+                                            M, T, K, _lib.F64, self._st()), "assx_psdtf_loss")
+        return loss
+
+    def psdtf_reconstruct(self, V, H, out=None):
+        """(B,T,M,M): sum_k H V_k."""
+        B, M, T, K = self._psdtf_dims(V, H)
+        Xh = out if out is not None else self.empty((B, T, M, M), dtype=torch.float64)
+        self._psdtf_array(Xh, (B, T, M, M), "out")
+        self._check(self._L.assx_psdtf_reconstruct(self.ctx, ptr(V), ptr(H), ptr(Xh), B, M, T, K, _lib.F64, self._st()),
+                    "assx_psdtf_reconstruct")
+        return Xh
+
+    def psdtf_iterate(self, n_iter, X, V, H, ws, eps=1e-12, normalize=True, loss=None, status=None):
+        """n_iter x (update, loss); loss: (n_iter, B) float64 or None."""
+        B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
+        if int(n_iter) < 0:
+            raise ValueError("LDPSDTF: n_iter must be >= 0, got %d" % int(n_iter))
+        if loss is not None:
+            self._psdtf_array(loss, (int(n_iter), B), "loss")
+        self._check(self._L.assx_psdtf_iterate(self.ctx, int(n_iter), ptr(X), ptr(V), ptr(H), float(eps),
+                                               int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), B, M, T, K, _lib.F64,
+                                               self._st()), "assx_psdtf_iterate")
+
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""
         if A.dim() != 3 or tuple(Bm.shape) != tuple(A.shape) or A.shape[1] != A.shape[2]:

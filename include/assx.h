@@ -81,7 +81,8 @@ enum { ASSX_E_ARG = -1, ASSX_E_UNSUPPORTED = -2, ASSX_E_NULL = -3 };
 /* status flags (device int32 per utterance) */
 enum {
   ASSX_STATUS_SINGULAR = 1, /* an exactly singular W U_n met in IP: numpy.linalg.solve would raise LinAlgError */
-  ASSX_STATUS_COND_REJECT = 2 /* informational: at least one bin kept its old row (cond >= threshold) */
+  ASSX_STATUS_COND_REJECT = 2, /* informational: at least one bin kept its old row (cond >= threshold) */
+  ASSX_STATUS_NOT_CONVERGED = 4 /* a Jacobi eigen-solve of (f9) ran out of sweeps */
 };
 
 /* weight kinds for assx_cov_accumulate */
@@ -435,6 +436,45 @@ int assx_ntf_reconstruct(assx_ctx* ctx, const void* Z, const void* Tb, const voi
 int assx_ntf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* Z, void* Tb, void* V, double eps,
                      double* loss /* (n_iter,B) or NULL */, void* ws, int B, int N, int I, int J, int K, int dtype,
                      void* stream);
+
+/* ---- (f9) LDPSDTF, log-det positive semidefinite tensor factorisation (src/algorithm/psdtf.py:88-176) ---------------------
+ * Model Y_t = sum_k H[k,t] V_k for T real symmetric M x M matrices.  State (float64 only, matrices contiguous): X (B,T,M,M)
+ * target, V (B,K,M,M) basis (symmetric), H (B,K,T) activation.  1 <= M <= 64, 1 <= K <= 64, B, T >= 1, B T < 2^24 and
+ * B < 2^16 (one workgroup per frame or basis, a launch holds fewer than 2^32 threads; n_mat < 2^24 likewise) (ASSX_E_ARG
+ * outside), dtype ASSX_F64 (ASSX_F32: ASSX_E_UNSUPPORTED).  `ws` (assx_psdtf_workspace_bytes; 0 for an empty or unsupported
+ * problem, no GPU needed) is scratch.  psd(A) is the reference's to_PSD: (A + A^T) / 2 - min(lambda_min, 0) I + eps tr I.
+ * `status` (B,) int32 or NULL: ASSX_STATUS_SINGULAR where a matrix the method inverts or factors is not positive definite
+ * (numpy.linalg raises LinAlgError there), ASSX_STATUS_NOT_CONVERGED where an eigen-solve ran out of sweeps; the kernels
+ * finish either way.  No float atomics and no partition that depends on B: results are bit-reproducible and a batch equals
+ * its single calls bit for bit.
+ *   assx_psdtf_to_psd             psd() of n_mat M x M matrices, in place.
+ *   assx_psdtf_update_basis       psdtf.py:120-154: Y = psd(sum_k H V_k), Yi = psd(Y^-1), Z = psd(Yi X Yi) per frame;
+ *                                 P_k = psd(sum_t H Yi), Q_k = psd(sum_t H Z), L = chol(Q), C = psd(L^T V P V L),
+ *                                 S = psd(C^1/2)^-1, V <- psd(V L S L^T V) per basis.
+ *   assx_psdtf_update_activation  psdtf.py:156-176: H <- H sqrt(max(tr(Yi V_k Yi X), 0) / max(tr(Yi V_k), eps)).
+ *   assx_psdtf_normalize          V_k /= tr V_k, H[k,:] *= tr V_k.
+ *   assx_psdtf_update             the three above in this order (the last one if `normalize`).
+ *   assx_psdtf_loss               loss (B,) = sum_t tr(X Y^-1) - (logdet X - logdet Y) - M, Y = psd(sum_k H V_k), both sets
+ *                                 of eigenvalues floored at eps.
+ *   assx_psdtf_reconstruct        Xh (B,T,M,M) = sum_k H V_k, without psd().
+ *   assx_psdtf_iterate            n_iter x (assx_psdtf_update, then assx_psdtf_loss into loss[i] if loss != NULL), enqueued
+ *                                 without a synchronisation, bit for bit the result of the single calls. */
+size_t assx_psdtf_workspace_bytes(int B, int M, int T, int K, int dtype);
+int assx_psdtf_to_psd(assx_ctx* ctx, void* A /* (n_mat,M,M) */, int n_mat, int M, double eps, void* stream);
+int assx_psdtf_update_basis(assx_ctx* ctx, const void* X, void* V, const void* H, double eps, int32_t* status, void* ws,
+                            int B, int M, int T, int K, int dtype, void* stream);
+int assx_psdtf_update_activation(assx_ctx* ctx, const void* X, const void* V, void* H, double eps, int32_t* status, int B,
+                                 int M, int T, int K, int dtype, void* stream);
+int assx_psdtf_normalize(assx_ctx* ctx, void* V, void* H, int B, int M, int T, int K, int dtype, void* stream);
+int assx_psdtf_update(assx_ctx* ctx, const void* X, void* V, void* H, double eps, int normalize, int32_t* status, void* ws,
+                      int B, int M, int T, int K, int dtype, void* stream);
+int assx_psdtf_loss(assx_ctx* ctx, const void* X, const void* V, const void* H, double eps, double* loss /* (B,) */,
+                    int32_t* status, void* ws, int B, int M, int T, int K, int dtype, void* stream);
+int assx_psdtf_reconstruct(assx_ctx* ctx, const void* V, const void* H, void* Xh, int B, int M, int T, int K, int dtype,
+                           void* stream);
+int assx_psdtf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* V, void* H, double eps, int normalize,
+                       double* loss /* (n_iter,B) or NULL */, int32_t* status, void* ws, int B, int M, int T, int K,
+                       int dtype, void* stream);
 
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
