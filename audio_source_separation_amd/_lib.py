@@ -101,6 +101,15 @@ SIGNATURES = {
     "assx_psdtf_loss": (_i, [_vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_psdtf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_psdtf_iterate": (_i, [_vp, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "assx_ipsdta_to_psd": (_i, [_vp, _vp, _i, _i, _d, _vp]),
+    "assx_ipsdta_update_basis": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_update_activation": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_normalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_update_source": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_update_spatial": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_ipsdta_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

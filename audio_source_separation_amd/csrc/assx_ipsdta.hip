@@ -1,0 +1,894 @@
+// GaussIPSDTA, Kondo's block-diagonal independent positive semidefinite tensor analysis (src/bss/ipsdta.py:510-688,
+// 820-1081) on MI355X: MM source model, vectorwise coordinate descent (VCD) spatial model, loss.  float64 / complex128.
+//
+// The n_bins bins are cut into n_blocks blocks: the first nlow = n_blocks - n_bins % n_blocks of nn = n_bins / n_blocks
+// bins, the rest of nn + 1.  Block b has size nb, first bin f0 and packed offset off (the nb x nb matrices of all blocks
+// laid end to end, P = sum nb^2 entries).  State: X (M,F,T) complex input, W (F,M,M) complex demixing filter,
+// U (N,K,P) complex packed Hermitian bases, H (N,K,T) activation, N = M.  psd(A) = (A + A^H)/2 - min(lambda_min, 0) I +
+// eps tr I follows every matrix the reference applies to_PSD to.  With y = W x the block's output,
+//
+//   ip_model_kernel<NB, MODE>  one thread per (source, block, frame), matrices in registers (assx_herm_linalg.hpp):
+//                     R = psd(sum_k H U_k), Ri = psd(R^-1) (Cholesky); BASIS: Ri and Z = Ri (y y^H + eps I) Ri go to the
+//                     workspace as (N,P,T), frames fastest; ACT: Ri and G = Ri psd(y y^H + eps I) Ri; SPATIAL: Ri;
+//                     LOSS: y^H Ri y + sum log max(lambda(R), eps) per (source, block, frame)
+//   ip_contract_kernel  S_k = sum_t H Z, T_k = sum_t H Ri: one wave per (source, entry), its lanes stride the frames, 8
+//                     bases at a time, a butterfly adds the lanes
+//   ip_basis_kernel<NB>  one thread per (source, basis, block): U <- psd(U S^1/2 psd(psd(psd(S^1/2 U T U S^1/2)^1/2)^-1)
+//                     S^1/2 U), S^1/2 = psd of the Jacobi square root
+//   ip_act_kernel     one thread per (source, basis, frame): num = sum_e Re(U_k[e] conj(G[e])), den likewise with Ri, in
+//                     entry order; H <- H sqrt(max(num, 0) / max(den, eps))
+//   ip_norm_kernel    one workgroup per (source, basis): U_k /= tr U_k, H[k,:] *= tr U_k
+//   ip_q_kernel       Q[n,f] = mean_t (Ri)_ii(t) (x x^H + eps |x|^2 I), one wave per (source, bin), one lane per entry,
+//                     the frames in index order; ip_qpsd_kernel<M> applies psd.  Q depends on neither W nor the sweep
+//   ip_sweep_kernel   one workgroup per block, one VCD sweep: sources in order, positions of the block in order
+//                     (Gauss-Seidel); gamma by all threads over the frames, the two M x M solves and the row update by
+//                     thread 0; the block's rows of W live in LDS
+//   ip_loss_kernel    one workgroup: the per-(source, block, frame) terms in index order and -2 T log|det W_f| (LU)
+//
+// The psd() of x x^H takes min(lambda_min, 0) as 0 (lambda_min of a rank-one matrix is rounding noise), and so does the one
+// of y y^H + eps I.  A block that is not positive definite where the method inverts it, or a singular solve, sets
+// ASSX_STATUS_SINGULAR; the kernels finish either way.  No float atomics, no partition that depends on anything but the
+// shapes, every sum in a fixed order.
+#include "assx_common.hpp"
+#include "assx_herm_linalg.hpp"
+
+using namespace assx;
+using herm::Mat;
+
+namespace {
+
+constexpr int BLK = 256;
+constexpr int NW = BLK / WAVE;
+constexpr int NBMAX = 8;
+constexpr int MMAX = 8;
+constexpr int KMAX = 64;
+constexpr int KC = 8;
+constexpr int ST_SINGULAR = 1;
+
+typedef double2 cx;
+
+struct IpGeo {
+  int M, F, T, K, nblk, nn, nlow, P;
+};
+
+struct IpBlock {
+  int nb, f0, off;
+};
+
+__host__ __device__ inline IpBlock ip_block(const IpGeo& g, int b) {
+  IpBlock r;
+  if (b < g.nlow) {
+    r.nb = g.nn, r.f0 = b * g.nn, r.off = b * g.nn * g.nn;
+  } else {
+    const int h = b - g.nlow, n1 = g.nn + 1;
+    r.nb = n1, r.f0 = g.nlow * g.nn + h * n1, r.off = g.nlow * g.nn * g.nn + h * n1 * n1;
+  }
+  return r;
+}
+
+// false outside the envelope of include/assx.h (f10)
+inline bool ip_geo(int M, int F, int T, int K, int n_blocks, IpGeo& g) {
+  if (M < 2 || M > MMAX || K < 1 || K > KMAX || T < 1 || F < 1 || n_blocks < 1 || n_blocks > F) return false;
+  const int nn = F / n_blocks, rem = F % n_blocks;
+  if (nn + (rem > 0) > NBMAX || F > (1 << 20) || T > (1 << 24)) return false;
+  g.M = M, g.F = F, g.T = T, g.K = K, g.nblk = n_blocks, g.nn = nn, g.nlow = n_blocks - rem;
+  g.P = g.nlow * nn * nn + rem * (nn + 1) * (nn + 1);
+  // one thread per (source, block, frame): fewer than 2^31 of them
+  return (long long)M * n_blocks * T < (1LL << 31) && (long long)M * g.P * T < (1LL << 40);
+}
+
+struct IpLayout {
+  size_t ri, zz, part, q, lossp, total;
+};
+
+// ri, zz: (N,P,T) complex; part: S and T (N,2,K,P) complex; q: (N,F,M,M) complex; lossp: (N,n_blocks,T) double
+IpLayout ip_layout(const IpGeo& g) {
+  const size_t c = sizeof(cx), N = g.M;
+  IpLayout L;
+  L.ri = 0;
+  L.zz = L.ri + N * g.P * g.T * c;
+  L.part = L.zz + N * g.P * g.T * c;
+  L.q = L.part + N * 2 * g.K * g.P * c;
+  L.lossp = L.q + N * g.F * g.M * g.M * c;
+  L.total = L.lossp + N * g.nblk * g.T * sizeof(double);
+  return L;
+}
+
+__device__ __forceinline__ cx cmul(cx a, cx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ cx cmulc(cx a, cx b) {  // a conj(b)
+  return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
+__device__ __forceinline__ cx cdiv(cx a, cx b) {
+  const double d = b.x * b.x + b.y * b.y;
+  return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
+}
+// the principal square root
+__device__ __forceinline__ cx csqrt_(cx z) {
+  const double r = hypot(z.x, z.y);
+  if (r == 0.0) return make_double2(0.0, 0.0);
+  if (z.x >= 0.0) {
+    const double re = sqrt(0.5 * (r + z.x));
+    return make_double2(re, z.y / (2.0 * re));
+  }
+  const double im = copysign(sqrt(0.5 * (r - z.x)), z.y);
+  return make_double2(z.y / (2.0 * im), im);
+}
+
+// the eigenvalues of the Hermitian C (full storage, destroyed) by the cyclic Jacobi rotations of herm::herm_sqrt_psd
+template <int N>
+__device__ inline void ip_eigvals(Mat<N>& C, double (&w)[N]) {
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    double off = 0.0, tot = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      tot += C.re[i][i] * C.re[i][i];
+#pragma unroll
+      for (int j = 0; j < i; ++j) off += C.re[i][j] * C.re[i][j] + C.im[i][j] * C.im[i][j];
+    }
+    if (!(off > 1e-32 * (tot + 2.0 * off))) break;
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double ar = C.re[p][q], ai = C.im[p][q];
+        const double g = sqrt(ar * ar + ai * ai);
+        if (g == 0.0) continue;
+        const double er = ar / g, ei = ai / g;
+        const double theta = (C.re[q][q] - C.re[p][p]) / (2.0 * g);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double pr = C.re[k][p], pi = C.im[k][p], qr = C.re[k][q], qi = C.im[k][q];
+          const double wr = er * qr + ei * qi, wi = er * qi - ei * qr;
+          C.re[k][p] = c * pr - s * wr, C.im[k][p] = c * pi - s * wi;
+          C.re[k][q] = s * pr + c * wr, C.im[k][q] = s * pi + c * wi;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double pr = C.re[p][k], pi = C.im[p][k], qr = C.re[q][k], qi = C.im[q][k];
+          const double wr = er * qr - ei * qi, wi = er * qi + ei * qr;
+          C.re[p][k] = c * pr - s * wr, C.im[p][k] = c * pi - s * wi;
+          C.re[q][k] = s * pr + c * wr, C.im[q][k] = s * pi + c * wi;
+        }
+        C.re[p][q] = 0.0, C.im[p][q] = 0.0, C.re[q][p] = 0.0, C.im[q][p] = 0.0;
+        C.im[p][p] = 0.0, C.im[q][q] = 0.0;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = C.re[i][i];
+}
+
+// A <- (A + A^H)/2 - min(lambda_min, 0) I + eps tr I.  A Cholesky factorisation with every pivot above 2^-40 of the
+// largest diagonal entry proves lambda_min > 0 (the shortcut of sl::to_psd); otherwise lambda_min comes from Jacobi.
+template <int N>
+__device__ inline void ip_psd(Mat<N>& A, double eps) {
+  herm::hermitize(A);
+  double tr = 0.0, mx = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) tr += A.re[i][i], mx = fmax(mx, A.re[i][i]);
+  Mat<N> L = A;
+  bool ok = herm::herm_cholesky(L);
+  const double fl = ldexp(mx, -40);
+#pragma unroll
+  for (int i = 0; i < N; ++i) ok = ok && L.re[i][i] * L.re[i][i] > fl;
+  double delta = 0.0;
+  if (!ok) {
+    L = A;
+    double w[N];
+    ip_eigvals(L, w);
+#pragma unroll
+    for (int i = 0; i < N; ++i) delta = fmin(delta, w[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) A.re[i][i] = (A.re[i][i] - delta) + eps * tr;
+}
+
+// Ai = A^-1 of a Hermitian positive definite A (destroyed) by Cholesky; false when a pivot is not positive
+template <int N>
+__device__ inline bool ip_inv(Mat<N>& A, Mat<N>& Ai) {
+  const bool ok = herm::herm_cholesky(A);
+  Mat<N> Li;
+  herm::tri_inverse(A, Li);
+  herm::matmul_ah(Li, Li, Ai);
+  return ok;
+}
+
+template <int N>
+__device__ inline void ip_load(const cx* __restrict__ p, Mat<N>& A) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const cx v = p[i * N + j];
+      A.re[i][j] = v.x, A.im[i][j] = v.y;
+    }
+}
+
+template <int N>
+__device__ inline void ip_store(const Mat<N>& A, cx* __restrict__ p) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) p[i * N + j] = make_double2(A.re[i][j], A.im[i][j]);
+}
+
+// entry e of a frame-fastest (N,P,T) array
+template <int N>
+__device__ inline void ip_store_t(const Mat<N>& A, cx* __restrict__ p, size_t T) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) p[(size_t)(i * N + j) * T] = make_double2(A.re[i][j], A.im[i][j]);
+}
+
+__device__ __forceinline__ void ip_flag(int32_t* status, bool bad) {
+  if (bad && status) atomicOr(status, ST_SINGULAR);
+}
+
+enum { MODE_BASIS = 0, MODE_ACT = 1, MODE_SPATIAL = 2, MODE_LOSS = 3 };
+
+// blocks b0 .. b0 + nbk - 1, all of size NB
+template <int NB, int MODE>
+__global__ void __launch_bounds__(BLK) ip_model_kernel(const cx* __restrict__ X, const cx* __restrict__ W,
+                                                       const cx* __restrict__ U, const double* __restrict__ H,
+                                                       cx* __restrict__ ri, cx* __restrict__ zz,
+                                                       double* __restrict__ lossp, int32_t* status, double eps, IpGeo g,
+                                                       int b0, int nbk) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+  const size_t T = g.T;
+  if (idx >= (size_t)g.M * nbk * T) return;
+  const int t = (int)(idx % T), b = b0 + (int)((idx / T) % nbk), n = (int)(idx / (T * nbk));
+  const IpBlock bk = ip_block(g, b);
+  Mat<NB> R;
+  herm::set_zero(R);
+  for (int k = 0; k < g.K; ++k) {
+    const double h = H[((size_t)n * g.K + k) * T + t];
+    const cx* Uk = U + ((size_t)n * g.K + k) * g.P + bk.off;
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const cx u = Uk[i * NB + j];
+        R.re[i][j] += h * u.x, R.im[i][j] += h * u.y;
+      }
+  }
+  ip_psd(R, eps);
+  double ld = 0.0;
+  if (MODE == MODE_LOSS) {
+    Mat<NB> E = R;
+    double w[NB];
+    ip_eigvals(E, w);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) ld += log(fmax(w[i], eps));
+  }
+  Mat<NB> Ri;
+  const bool ok = ip_inv(R, Ri);
+  ip_psd(Ri, eps);
+  ip_flag(status, !ok);
+  // y = W x of the block's bins, v = Ri y
+  double yr[NB], yi[NB], vr[NB], vi[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int f = bk.f0 + i;
+    cx acc = make_double2(0.0, 0.0);
+    for (int c = 0; c < g.M; ++c) {
+      const cx p = cmul(W[((size_t)f * g.M + n) * g.M + c], X[((size_t)c * g.F + f) * T + t]);
+      acc.x += p.x, acc.y += p.y;
+    }
+    yr[i] = acc.x, yi[i] = acc.y;
+  }
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    double sr = 0.0, si = 0.0;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      sr += Ri.re[i][j] * yr[j] - Ri.im[i][j] * yi[j];
+      si += Ri.re[i][j] * yi[j] + Ri.im[i][j] * yr[j];
+    }
+    vr[i] = sr, vi[i] = si;
+  }
+  if (MODE == MODE_LOSS) {
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) q += yr[i] * vr[i] + yi[i] * vi[i];
+    lossp[((size_t)n * g.nblk + b) * T + t] = q + ld;
+    return;
+  }
+  ip_store_t(Ri, ri + ((size_t)n * g.P + bk.off) * T + t, T);
+  if (MODE == MODE_BASIS || MODE == MODE_ACT) {
+    // Ri (y y^H + c I) Ri = v v^H + c Ri Ri for the Hermitian Ri; c = eps, and for ACT the eps-trace shift of psd on top
+    double c = eps;
+    if (MODE == MODE_ACT) {
+      double tr = 0.0;
+#pragma unroll
+      for (int i = 0; i < NB; ++i) tr += (yr[i] * yr[i] + yi[i] * yi[i]) + eps;
+      c = eps + eps * tr;
+    }
+    Mat<NB> Z;
+    herm::matmul(Ri, Ri, Z);
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        Z.re[i][j] = c * Z.re[i][j] + (vr[i] * vr[j] + vi[i] * vi[j]);
+        Z.im[i][j] = c * Z.im[i][j] + (vi[i] * vr[j] - vr[i] * vi[j]);
+      }
+    ip_store_t(Z, zz + ((size_t)n * g.P + bk.off) * T + t, T);
+  }
+}
+
+// one wave per (source, entry): part[n][0][k][e] = sum_t H[n,k,t] zz[n,e,t], part[n][1][k][e] the same with ri
+__global__ void __launch_bounds__(BLK) ip_contract_kernel(const double* __restrict__ H, const cx* __restrict__ ri,
+                                                          const cx* __restrict__ zz, cx* __restrict__ part, IpGeo g) {
+  const size_t wv = (size_t)blockIdx.x * NW + threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (wv >= (size_t)g.M * g.P) return;
+  const size_t n = wv / g.P, e = wv % g.P, T = g.T;
+  const cx *zrow = zz + wv * T, *rrow = ri + wv * T;
+  for (int k0 = 0; k0 < g.K; k0 += KC) {
+    double s[KC][2], r[KC][2];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) s[c][0] = s[c][1] = r[c][0] = r[c][1] = 0.0;
+    for (size_t t = lane; t < T; t += WAVE) {
+      const cx z = zrow[t], q = rrow[t];
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const double h = H[(n * g.K + min(k0 + c, g.K - 1)) * T + t];
+        s[c][0] += h * z.x, s[c][1] += h * z.y, r[c][0] += h * q.x, r[c][1] += h * q.y;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      for (int o = WAVE / 2; o > 0; o >>= 1) {
+        s[c][0] += __shfl_xor(s[c][0], o), s[c][1] += __shfl_xor(s[c][1], o);
+        r[c][0] += __shfl_xor(r[c][0], o), r[c][1] += __shfl_xor(r[c][1], o);
+      }
+      if (lane == 0 && k0 + c < g.K) {
+        part[((n * 2 + 0) * g.K + k0 + c) * g.P + e] = make_double2(s[c][0], s[c][1]);
+        part[((n * 2 + 1) * g.K + k0 + c) * g.P + e] = make_double2(r[c][0], r[c][1]);
+      }
+    }
+  }
+}
+
+template <int NB>
+__global__ void __launch_bounds__(BLK) ip_basis_kernel(cx* __restrict__ U, const cx* __restrict__ part, int32_t* status,
+                                                       double eps, IpGeo g, int b0, int nbk) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+  if (idx >= (size_t)g.M * g.K * nbk) return;
+  const int b = b0 + (int)(idx % nbk), k = (int)((idx / nbk) % g.K), n = (int)(idx / ((size_t)nbk * g.K));
+  const IpBlock bk = ip_block(g, b);
+  cx* Up = U + ((size_t)n * g.K + k) * g.P + bk.off;
+  Mat<NB> A, Bm, C, Uk, sq;
+  ip_load(part + (((size_t)n * 2 + 0) * g.K + k) * g.P + bk.off, A);  // S
+  herm::hermitize(A);
+  herm::herm_sqrt_psd(A, sq);
+  ip_psd(sq, eps);
+  ip_load(Up, Uk);
+  ip_load(part + (((size_t)n * 2 + 1) * g.K + k) * g.P + bk.off, Bm);  // T
+  herm::matmul(sq, Uk, A);
+  herm::matmul(A, Bm, C);
+  herm::matmul(C, Uk, A);
+  herm::matmul(A, sq, C);  // S^1/2 U T U S^1/2
+  ip_psd(C, eps);
+  herm::herm_sqrt_psd(C, A);
+  ip_psd(A, eps);
+  const bool ok = ip_inv(A, Bm);
+  ip_psd(Bm, eps);
+  ip_flag(status, !ok);
+  herm::matmul(Uk, sq, A);
+  herm::matmul(A, Bm, C);
+  herm::matmul(C, sq, A);
+  herm::matmul(A, Uk, C);  // U S^1/2 (.)^-1 S^1/2 U
+  ip_psd(C, eps);
+  ip_store(C, Up);
+}
+
+// G in zz, Ri in ri (both from the new U)
+__global__ void __launch_bounds__(BLK) ip_act_kernel(const cx* __restrict__ U, double* __restrict__ H,
+                                                     const cx* __restrict__ ri, const cx* __restrict__ zz, double eps,
+                                                     IpGeo g) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x, T = g.T;
+  if (idx >= (size_t)g.M * g.K * T) return;
+  const size_t t = idx % T, nk = idx / T, n = nk / g.K;
+  const cx* Uk = U + nk * g.P;
+  double num = 0.0, den = 0.0;
+  for (int e = 0; e < g.P; ++e) {
+    const cx u = Uk[e], z = zz[(n * g.P + e) * T + t], r = ri[(n * g.P + e) * T + t];
+    num += u.x * z.x + u.y * z.y;
+    den += u.x * r.x + u.y * r.y;
+  }
+  H[idx] = H[idx] * sqrt(fmax(num, 0.0) / fmax(den, eps));
+}
+
+__device__ __forceinline__ double ip_block_sum(double v, double* red) {
+  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ void __launch_bounds__(BLK) ip_norm_kernel(cx* __restrict__ U, double* __restrict__ H, IpGeo g) {
+  __shared__ double red[NW];
+  const size_t nk = blockIdx.x;
+  cx* Uk = U + nk * g.P;
+  double tr = 0.0;
+  for (int b = threadIdx.x; b < g.nblk; b += BLK) {
+    const IpBlock bk = ip_block(g, b);
+    for (int i = 0; i < bk.nb; ++i) tr += Uk[bk.off + i * bk.nb + i].x;
+  }
+  tr = ip_block_sum(tr, red);
+  for (int e = threadIdx.x; e < g.P; e += BLK) Uk[e] = make_double2(Uk[e].x / tr, Uk[e].y / tr);
+  for (int t = threadIdx.x; t < g.T; t += BLK) H[nk * g.T + t] = H[nk * g.T + t] * tr;
+}
+
+// one wave per (source, bin), lane = entry (c, d)
+__global__ void __launch_bounds__(WAVE) ip_q_kernel(const cx* __restrict__ X, const cx* __restrict__ ri, cx* __restrict__ Q,
+                                                    double eps, IpGeo g) {
+  const int n = blockIdx.x / g.F, f = blockIdx.x % g.F;
+  const int c = threadIdx.x >> 3, d = threadIdx.x & 7;
+  if (c >= g.M || d >= g.M) return;
+  // the block and the position of bin f
+  const int split = g.nlow * g.nn;
+  const int b = f < split ? f / g.nn : g.nlow + (f - split) / (g.nn + 1);
+  const IpBlock bk = ip_block(g, b);
+  const int i = f - bk.f0;
+  const size_t T = g.T;
+  const cx* w = ri + ((size_t)n * g.P + bk.off + i * bk.nb + i) * T;
+  const cx *xc = X + ((size_t)c * g.F + f) * T, *xd = X + ((size_t)d * g.F + f) * T;
+  double re = 0.0, im = 0.0;
+  for (size_t t = 0; t < T; ++t) {
+    const double wt = w[t].x;
+    const cx a = xc[t], bb = xd[t];
+    double pr = a.x * bb.x + a.y * bb.y;
+    const double pi = a.y * bb.x - a.x * bb.y;
+    if (c == d) {
+      double tr = 0.0;
+      for (int m = 0; m < g.M; ++m) {
+        const cx v = X[((size_t)m * g.F + f) * T + t];
+        tr += v.x * v.x + v.y * v.y;
+      }
+      pr += eps * tr;
+    }
+    re += wt * pr, im += wt * pi;
+  }
+  Q[(((size_t)n * g.F + f) * g.M + c) * g.M + d] = make_double2(re / (double)g.T, im / (double)g.T);
+}
+
+template <int N>
+__global__ void __launch_bounds__(BLK) ip_topsd_kernel(cx* __restrict__ A, size_t n_mat, double eps) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
+  if (idx >= n_mat) return;
+  Mat<N> Am;
+  ip_load(A + idx * N * N, Am);
+  ip_psd(Am, eps);
+  ip_store(Am, A + idx * N * N);
+}
+
+// a[M][M] x = b in place (b becomes x), LU with partial pivoting (pivot by |re| + |im|); false on a zero pivot
+__device__ inline bool ip_solve(int M, cx (*a)[MMAX], cx* b) {
+  bool ok = true;
+  for (int j = 0; j < M; ++j) {
+    int p = j;
+    double best = fabs(a[j][j].x) + fabs(a[j][j].y);
+    for (int i = j + 1; i < M; ++i) {
+      const double v = fabs(a[i][j].x) + fabs(a[i][j].y);
+      if (v > best) best = v, p = i;
+    }
+    if (!(best > 0.0)) ok = false;
+    if (p != j) {
+      for (int c = 0; c < M; ++c) {
+        const cx tmp = a[j][c];
+        a[j][c] = a[p][c], a[p][c] = tmp;
+      }
+      const cx tmp = b[j];
+      b[j] = b[p], b[p] = tmp;
+    }
+    for (int i = j + 1; i < M; ++i) {
+      const cx l = cdiv(a[i][j], a[j][j]);
+      for (int c = j + 1; c < M; ++c) {
+        const cx m = cmul(l, a[j][c]);
+        a[i][c].x -= m.x, a[i][c].y -= m.y;
+      }
+      const cx m = cmul(l, b[j]);
+      b[i].x -= m.x, b[i].y -= m.y;
+    }
+  }
+  for (int i = M - 1; i >= 0; --i) {
+    cx s = b[i];
+    for (int c = i + 1; c < M; ++c) {
+      const cx m = cmul(a[i][c], b[c]);
+      s.x -= m.x, s.y -= m.y;
+    }
+    b[i] = cdiv(s, a[i][i]);
+  }
+  return ok;
+}
+
+// ipsdta.py:946-971 for source n, position i of one block: Wl[i][n][:] <- conj(weight zeta - zeta_hat)
+__device__ inline bool ip_vcd_row(int M, int n, cx (*Wi)[MMAX], const cx* __restrict__ Qg, const cx* gam, double eps) {
+  cx a[MMAX][MMAX], q[MMAX][MMAX], zeta[MMAX], zh[MMAX], u[MMAX];
+  for (int c = 0; c < M; ++c)
+    for (int d = 0; d < M; ++d) q[c][d] = Qg[c * M + d];
+  for (int r = 0; r < M; ++r)
+    for (int d = 0; d < M; ++d) {
+      cx s = make_double2(0.0, 0.0);
+      for (int c = 0; c < M; ++c) {
+        const cx m = cmul(Wi[r][c], q[c][d]);
+        s.x += m.x, s.y += m.y;
+      }
+      a[r][d] = s;
+    }
+  for (int c = 0; c < M; ++c) zeta[c] = make_double2(c == n ? 1.0 : 0.0, 0.0), zh[c] = gam[c];
+  bool ok = ip_solve(M, a, zeta);
+  for (int c = 0; c < M; ++c)
+    for (int d = 0; d < M; ++d) a[c][d] = q[c][d];
+  ok = ip_solve(M, a, zh) && ok;
+  for (int d = 0; d < M; ++d) {  // u = zeta^H Q
+    cx s = make_double2(0.0, 0.0);
+    for (int c = 0; c < M; ++c) {
+      const cx m = cmulc(q[c][d], zeta[c]);
+      s.x += m.x, s.y += m.y;
+    }
+    u[d] = s;
+  }
+  cx eta = make_double2(0.0, 0.0), etah = make_double2(0.0, 0.0);
+  for (int d = 0; d < M; ++d) {
+    const cx m = cmul(u[d], zeta[d]), mh = cmul(u[d], zh[d]);
+    eta.x += m.x, eta.y += m.y, etah.x += mh.x, etah.y += mh.y;
+  }
+  if (hypot(eta.x, eta.y) < eps) eta = make_double2(eps, 0.0);
+  const double ah = hypot(etah.x, etah.y);
+  cx wt;
+  if (ah < eps) {
+    wt = cdiv(make_double2(1.0, 0.0), csqrt_(eta));
+  } else {
+    const double a2 = ah * ah;
+    const cx root = csqrt_(make_double2(1.0 + 4.0 * eta.x / a2, 4.0 * eta.y / a2));
+    const cx lead = cdiv(etah, make_double2(2.0 * eta.x, 2.0 * eta.y));
+    wt = cmul(lead, make_double2(1.0 - root.x, -root.y));
+  }
+  for (int c = 0; c < M; ++c) {
+    const cx m = cmul(wt, zeta[c]);
+    Wi[n][c] = make_double2(m.x - zh[c].x, -(m.y - zh[c].y));
+  }
+  return ok;
+}
+
+__global__ void __launch_bounds__(BLK) ip_sweep_kernel(const cx* __restrict__ X, cx* __restrict__ W,
+                                                       const cx* __restrict__ ri, const cx* __restrict__ Q,
+                                                       int32_t* status, double eps, IpGeo g) {
+  __shared__ cx Wl[NBMAX][MMAX][MMAX];
+  __shared__ cx red[NW][MMAX];
+  __shared__ cx gam[MMAX];
+  const int b = blockIdx.x, M = g.M, tid = threadIdx.x;
+  const IpBlock bk = ip_block(g, b);
+  const int nb = bk.nb;
+  const size_t T = g.T;
+  for (int e = tid; e < nb * M * M; e += BLK) Wl[e / (M * M)][(e / M) % M][e % M] = W[(size_t)bk.f0 * M * M + e];
+  __syncthreads();
+  for (int n = 0; n < M; ++n) {
+    for (int i = 0; i < nb; ++i) {
+      double ar[MMAX], ai[MMAX];
+#pragma unroll
+      for (int c = 0; c < MMAX; ++c) ar[c] = 0.0, ai[c] = 0.0;
+      if (nb > 1) {
+        for (size_t t = tid; t < T; t += BLK) {
+          cx s = make_double2(0.0, 0.0);
+          for (int j = 0; j < nb; ++j) {
+            if (j == i) continue;
+            cx y = make_double2(0.0, 0.0);
+            for (int c = 0; c < M; ++c) {
+              const cx p = cmul(Wl[j][n][c], X[((size_t)c * g.F + bk.f0 + j) * T + t]);
+              y.x += p.x, y.y += p.y;
+            }
+            const cx p = cmulc(ri[((size_t)n * g.P + bk.off + j * nb + i) * T + t], y);
+            s.x += p.x, s.y += p.y;
+          }
+#pragma unroll
+          for (int c = 0; c < MMAX; ++c) {
+            if (c < M) {
+              const cx p = cmul(s, X[((size_t)c * g.F + bk.f0 + i) * T + t]);
+              ar[c] += p.x, ai[c] += p.y;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < MMAX; ++c) {
+        for (int o = WAVE / 2; o > 0; o >>= 1) ar[c] += __shfl_xor(ar[c], o), ai[c] += __shfl_xor(ai[c], o);
+        if ((tid & (WAVE - 1)) == 0) red[tid / WAVE][c] = make_double2(ar[c], ai[c]);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        for (int c = 0; c < M; ++c) {
+          const double sr = ((red[0][c].x + red[1][c].x) + red[2][c].x) + red[3][c].x;
+          const double si = ((red[0][c].y + red[1][c].y) + red[2][c].y) + red[3][c].y;
+          gam[c] = make_double2(sr / (double)g.T, si / (double)g.T);
+        }
+        const bool ok = ip_vcd_row(M, n, Wl[i], Q + ((size_t)n * g.F + bk.f0 + i) * M * M, gam, eps);
+        ip_flag(status, !ok);
+      }
+      __syncthreads();
+    }
+  }
+  for (int e = tid; e < nb * M * M; e += BLK) W[(size_t)bk.f0 * M * M + e] = Wl[e / (M * M)][(e / M) % M][e % M];
+}
+
+// loss = sum lossp - 2 T sum_f log max(|det W_f|, ...) with |det| from an LU: sum_i log max(|u_ii|, eps)
+__global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, const double* __restrict__ lossp,
+                                                      double* __restrict__ loss, double eps, IpGeo g) {
+  __shared__ double red[NW];
+  const size_t n_terms = (size_t)g.M * g.nblk * g.T;
+  double v = 0.0;
+  for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += lossp[e];
+  v = ip_block_sum(v, red);
+  double ldw = 0.0;
+  const int M = g.M;
+  for (int f = threadIdx.x; f < g.F; f += BLK) {
+    cx a[MMAX][MMAX];
+    for (int r = 0; r < M; ++r)
+      for (int c = 0; c < M; ++c) a[r][c] = W[((size_t)f * M + r) * M + c];
+    for (int j = 0; j < M; ++j) {
+      int p = j;
+      double best = fabs(a[j][j].x) + fabs(a[j][j].y);
+      for (int i = j + 1; i < M; ++i) {
+        const double s = fabs(a[i][j].x) + fabs(a[i][j].y);
+        if (s > best) best = s, p = i;
+      }
+      if (p != j)
+        for (int c = 0; c < M; ++c) {
+          const cx tmp = a[j][c];
+          a[j][c] = a[p][c], a[p][c] = tmp;
+        }
+      const double piv = hypot(a[j][j].x, a[j][j].y);
+      ldw += log(fmax(piv, eps));
+      if (piv > 0.0)
+        for (int i = j + 1; i < M; ++i) {
+          const cx l = cdiv(a[i][j], a[j][j]);
+          for (int c = j + 1; c < M; ++c) {
+            const cx m = cmul(l, a[j][c]);
+            a[i][c].x -= m.x, a[i][c].y -= m.y;
+          }
+        }
+    }
+  }
+  ldw = ip_block_sum(ldw, red);
+  if (threadIdx.x == 0) loss[0] = v - 2.0 * (double)g.T * ldw;
+}
+
+#define IP_NB_SWITCH(nb, ...)                                   \
+  switch (nb) {                                                 \
+    case 1: { constexpr int NB = 1; __VA_ARGS__; } break;       \
+    case 2: { constexpr int NB = 2; __VA_ARGS__; } break;       \
+    case 3: { constexpr int NB = 3; __VA_ARGS__; } break;       \
+    case 4: { constexpr int NB = 4; __VA_ARGS__; } break;       \
+    case 5: { constexpr int NB = 5; __VA_ARGS__; } break;       \
+    case 6: { constexpr int NB = 6; __VA_ARGS__; } break;       \
+    case 7: { constexpr int NB = 7; __VA_ARGS__; } break;       \
+    case 8: { constexpr int NB = 8; __VA_ARGS__; } break;       \
+    default: break;                                             \
+  }
+
+struct IpArgs {
+  const cx* X;
+  cx* W;
+  cx* U;
+  double* H;
+  double eps;
+  int32_t* status;
+  char* ws;
+  IpGeo g;
+  hipStream_t st;
+};
+
+inline unsigned ip_grid(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
+
+// the model kernel over the low blocks, then over the high ones
+template <int MODE>
+int ip_model(assx_ctx* ctx, const IpArgs& a) {
+  const IpGeo& g = a.g;
+  const IpLayout L = ip_layout(g);
+  cx *ri = (cx*)(a.ws + L.ri), *zz = (cx*)(a.ws + L.zz);
+  double* lossp = (double*)(a.ws + L.lossp);
+  for (int part = 0; part < 2; ++part) {
+    const int b0 = part ? g.nlow : 0, nbk = part ? g.nblk - g.nlow : g.nlow, nb = g.nn + part;
+    if (nbk == 0) continue;
+    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_model_kernel<NB, MODE>), dim3(ip_grid((size_t)g.M * nbk * g.T)), dim3(BLK), 0,
+                                        a.st, a.X, (const cx*)a.W, (const cx*)a.U, (const double*)a.H, ri, zz, lossp,
+                                        a.status, a.eps, g, b0, nbk));
+    ASSX_LAUNCH_CHECK(ctx, "ip_model_kernel");
+  }
+  return 0;
+}
+
+int ip_update_basis(assx_ctx* ctx, const IpArgs& a) {
+  const IpGeo& g = a.g;
+  const IpLayout L = ip_layout(g);
+  cx *ri = (cx*)(a.ws + L.ri), *zz = (cx*)(a.ws + L.zz), *part = (cx*)(a.ws + L.part);
+  int rc = ip_model<MODE_BASIS>(ctx, a);
+  if (rc) return rc;
+  const size_t waves = (size_t)g.M * g.P;
+  hipLaunchKernelGGL(ip_contract_kernel, dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st, (const double*)a.H,
+                     (const cx*)ri, (const cx*)zz, part, g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_contract_kernel");
+  for (int p = 0; p < 2; ++p) {
+    const int b0 = p ? g.nlow : 0, nbk = p ? g.nblk - g.nlow : g.nlow, nb = g.nn + p;
+    if (nbk == 0) continue;
+    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_basis_kernel<NB>), dim3(ip_grid((size_t)g.M * g.K * nbk)), dim3(BLK), 0, a.st,
+                                        a.U, (const cx*)part, a.status, a.eps, g, b0, nbk));
+    ASSX_LAUNCH_CHECK(ctx, "ip_basis_kernel");
+  }
+  return 0;
+}
+
+int ip_update_activation(assx_ctx* ctx, const IpArgs& a) {
+  const IpGeo& g = a.g;
+  const IpLayout L = ip_layout(g);
+  int rc = ip_model<MODE_ACT>(ctx, a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ip_act_kernel, dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
+                     (const cx*)(a.ws + L.ri), (const cx*)(a.ws + L.zz), a.eps, g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_act_kernel");
+  return 0;
+}
+
+int ip_normalize(assx_ctx* ctx, const IpArgs& a) {
+  hipLaunchKernelGGL(ip_norm_kernel, dim3((unsigned)(a.g.M * a.g.K)), dim3(BLK), 0, a.st, a.U, a.H, a.g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_norm_kernel");
+  return 0;
+}
+
+int ip_update_source(assx_ctx* ctx, const IpArgs& a, int normalize) {
+  int rc = ip_update_basis(ctx, a);
+  if (rc) return rc;
+  rc = ip_update_activation(ctx, a);
+  if (rc) return rc;
+  return normalize ? ip_normalize(ctx, a) : 0;
+}
+
+int ip_update_spatial(assx_ctx* ctx, const IpArgs& a, int n_sweeps) {
+  if (n_sweeps <= 0) return 0;
+  const IpGeo& g = a.g;
+  const IpLayout L = ip_layout(g);
+  cx *ri = (cx*)(a.ws + L.ri), *q = (cx*)(a.ws + L.q);
+  int rc = ip_model<MODE_SPATIAL>(ctx, a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ip_q_kernel, dim3((unsigned)(g.M * g.F)), dim3(WAVE), 0, a.st, a.X, (const cx*)ri, q, a.eps, g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_q_kernel");
+  const size_t nq = (size_t)g.M * g.F;
+  IP_NB_SWITCH(g.M, hipLaunchKernelGGL((ip_topsd_kernel<NB>), dim3(ip_grid(nq)), dim3(BLK), 0, a.st, q, nq, a.eps));
+  ASSX_LAUNCH_CHECK(ctx, "ip_topsd_kernel");
+  for (int s = 0; s < n_sweeps; ++s) {
+    hipLaunchKernelGGL(ip_sweep_kernel, dim3((unsigned)g.nblk), dim3(BLK), 0, a.st, a.X, a.W, (const cx*)ri, (const cx*)q,
+                       a.status, a.eps, g);
+    ASSX_LAUNCH_CHECK(ctx, "ip_sweep_kernel");
+  }
+  return 0;
+}
+
+int ip_loss(assx_ctx* ctx, const IpArgs& a, double* loss) {
+  const IpLayout L = ip_layout(a.g);
+  int rc = ip_model<MODE_LOSS>(ctx, a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ip_loss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)(a.ws + L.lossp), loss,
+                     a.eps, a.g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_loss_kernel");
+  return 0;
+}
+
+int ip_args(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, double eps, int32_t* status, void* ws, int M,
+            int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  ASSX_REQUIRE_CTX(ctx);
+  ASSX_REQUIRE(ctx, dtype == ASSX_F64 || dtype == ASSX_F32, ASSX_E_ARG, "bad dtype %d", dtype);
+  ASSX_REQUIRE(ctx, dtype == ASSX_F64, ASSX_E_UNSUPPORTED, "GaussIPSDTA: float64 only");
+  ASSX_REQUIRE(ctx, ip_geo(M, F, T, K, n_blocks, a.g), ASSX_E_ARG,
+               "GaussIPSDTA: M=%d F=%d T=%d K=%d n_blocks=%d outside the envelope (2 <= M <= 8, 1 <= K <= 64, 1 <= n_blocks "
+               "<= F, largest block <= 8)",
+               M, F, T, K, n_blocks);
+  a.X = (const cx*)X, a.W = (cx*)W, a.U = (cx*)U, a.H = (double*)H, a.eps = eps, a.status = status, a.ws = (char*)ws;
+  a.st = (hipStream_t)stream;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t assx_ipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype) {
+  IpGeo g;
+  if (dtype != ASSX_F64 || !ip_geo(M, F, T, K, n_blocks, g)) return 0;
+  return ip_layout(g).total;
+}
+
+int assx_ipsdta_to_psd(assx_ctx* ctx, void* A, int n_mat, int nb, double eps, void* stream) {
+  ASSX_REQUIRE_CTX(ctx);
+  ASSX_REQUIRE(ctx, n_mat >= 1 && nb >= 1 && nb <= NBMAX, ASSX_E_ARG,
+               "assx_ipsdta_to_psd: n_mat=%d nb=%d (n_mat >= 1, nb in [1, 8])", n_mat, nb);
+  ASSX_REQUIRE(ctx, A, ASSX_E_NULL, "assx_ipsdta_to_psd: NULL array");
+  IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_topsd_kernel<NB>), dim3(ip_grid((size_t)n_mat)), dim3(BLK), 0,
+                                      (hipStream_t)stream, (cx*)A, (size_t)n_mat, eps));
+  ASSX_LAUNCH_CHECK(ctx, "ip_topsd_kernel");
+  return 0;
+}
+
+int assx_ipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* U, const void* H, double eps, int32_t* status,
+                             void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, (void*)W, U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_basis: NULL array");
+  return ip_update_basis(ctx, a);
+}
+
+int assx_ipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps,
+                                  int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                  void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, (void*)W, (void*)U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_activation: NULL array");
+  return ip_update_activation(ctx, a);
+}
+
+int assx_ipsdta_normalize(assx_ctx* ctx, void* U, void* H, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, nullptr, nullptr, U, H, 0.0, nullptr, nullptr, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, U && H, ASSX_E_NULL, "assx_ipsdta_normalize: NULL array");
+  return ip_normalize(ctx, a);
+}
+
+int assx_ipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void* U, void* H, double eps, int normalize,
+                              int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, (void*)W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_source: NULL array");
+  return ip_update_source(ctx, a, normalize);
+}
+
+int assx_ipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
+                               int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, W, (void*)U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, n_sweeps >= 0, ASSX_E_ARG, "assx_ipsdta_update_spatial: n_sweeps = %d", n_sweeps);
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_spatial: NULL array");
+  return ip_update_spatial(ctx, a, n_sweeps);
+}
+
+int assx_ipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U, const void* H, double eps, double* loss,
+                     int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, (void*)W, (void*)U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && loss && ws, ASSX_E_NULL, "assx_ipsdta_loss: NULL array");
+  return ip_loss(ctx, a, loss);
+}
+
+int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
+                        int normalize, double* loss, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks,
+                        int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_args(ctx, a, X, W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, n_iter >= 0 && spatial_iteration >= 0, ASSX_E_ARG, "assx_ipsdta_iterate: n_iter = %d, spatial_iteration = %d",
+               n_iter, spatial_iteration);
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_iterate: NULL array");
+  for (int it = 0; it < n_iter; ++it) {
+    rc = ip_update_source(ctx, a, normalize);
+    if (rc) return rc;
+    rc = ip_update_spatial(ctx, a, spatial_iteration);
+    if (rc) return rc;
+    if (loss) {
+      rc = ip_loss(ctx, a, loss + it);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -807,6 +807,126 @@ class Engine:
                                                int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), B, M, T, K, _lib.F64,
                                                self._st()), "assx_psdtf_iterate")
 
+    # ------------------------------------------------------------------ GaussIPSDTA (include/assx.h (f10))
+    @staticmethod
+    def ipsdta_packed_size(F, n_blocks):
+        """P: the entries of one packed basis (the nb x nb blocks end to end)."""
+        nn, rem = F // n_blocks, F % n_blocks
+        return (n_blocks - rem) * nn * nn + rem * (nn + 1) * (nn + 1)
+
+    def _ipsdta_array(self, a, shape, name, dtype):
+        if a.dtype != dtype or a.device != self.dev:
+            raise ValueError("GaussIPSDTA: %s must be %s on %s, got %s on %s" % (name, dtype, self.dev, a.dtype, a.device))
+        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
+            raise ValueError("GaussIPSDTA: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
+
+    def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None):
+        """Shapes are checked here, where they are still known: the C-ABI takes pointers and sizes."""
+        if U.dim() != 3 or H.dim() != 3:
+            raise ValueError("GaussIPSDTA: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
+                             % (tuple(U.shape), tuple(H.shape)))
+        M, K, T = (int(d) for d in H.shape)
+        if X is not None:
+            F = int(X.shape[1])
+        elif W is not None:
+            F = int(W.shape[0])
+        else:
+            raise ValueError("GaussIPSDTA: the number of bins is unknown without X or W")
+        n_blocks = int(n_blocks)
+        need = self._L.assx_ipsdta_workspace_bytes(M, F, T, K, n_blocks, self.prec.code)
+        if need == 0:
+            raise ValueError("GaussIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
+                             "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
+                             "n_blocks=%d" % (self.prec.name, M, F, T, K, n_blocks))
+        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, n_blocks)), "basis", torch.complex128)
+        self._ipsdta_array(H, (M, K, T), "activation", torch.float64)
+        if X is not None:
+            self._ipsdta_array(X, (M, F, T), "input", torch.complex128)
+        if W is not None:
+            self._ipsdta_array(W, (F, M, M), "demix_filter", torch.complex128)
+        if ws is not None and (ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need):
+            raise ValueError("GaussIPSDTA: workspace of %d bytes, %d needed" % (ws.numel(), need))
+        if status is not None:
+            self._ipsdta_array(status, (1,), "status", torch.int32)
+        return M, F, T, K, n_blocks
+
+    def ipsdta_workspace(self, M, F, T, K, n_blocks):
+        n = self._L.assx_ipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code)
+        if n == 0:
+            raise ValueError("GaussIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
+                             "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
+                             "n_blocks=%d" % (self.prec.name, M, F, T, K, n_blocks))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def ipsdta_to_psd(self, A, eps=1e-12):
+        """to_PSD of (n, nb, nb) Hermitian matrices, in place."""
+        if A.dim() != 3 or A.shape[1] != A.shape[2] or not 1 <= int(A.shape[1]) <= 8 or int(A.shape[0]) < 1:
+            raise ValueError("ipsdta_to_psd: expected (n, nb, nb) with 1 <= nb <= 8, got %s" % (tuple(A.shape),))
+        self._ipsdta_array(A, tuple(A.shape), "A", torch.complex128)
+        self._check(self._L.assx_ipsdta_to_psd(self.ctx, ptr(A), int(A.shape[0]), int(A.shape[1]), float(eps), self._st()),
+                    "assx_ipsdta_to_psd")
+        return A
+
+    def ipsdta_update_basis(self, X, W, U, H, ws, n_blocks, eps=1e-12, status=None):
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_ipsdta_update_basis(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(status), ptr(ws),
+                                                     M, F, T, K, nb, _lib.F64, self._st()), "assx_ipsdta_update_basis")
+
+    def ipsdta_update_activation(self, X, W, U, H, ws, n_blocks, eps=1e-12, status=None):
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_ipsdta_update_activation(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(status),
+                                                          ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_ipsdta_update_activation")
+
+    def ipsdta_normalize(self, U, H, n_bins, n_blocks):
+        if U.dim() != 3 or H.dim() != 3:
+            raise ValueError("GaussIPSDTA: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
+                             % (tuple(U.shape), tuple(H.shape)))
+        M, K, T = (int(d) for d in H.shape)
+        F, nb = int(n_bins), int(n_blocks)
+        if self._L.assx_ipsdta_workspace_bytes(M, F, T, K, nb, self.prec.code) == 0:
+            raise ValueError("GaussIPSDTA: n_channels=%d n_bins=%d n_basis=%d n_blocks=%d outside the envelope" % (M, F, K, nb))
+        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, nb)), "basis", torch.complex128)
+        self._ipsdta_array(H, (M, K, T), "activation", torch.float64)
+        self._check(self._L.assx_ipsdta_normalize(self.ctx, ptr(U), ptr(H), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_ipsdta_normalize")
+
+    def ipsdta_update_source(self, X, W, U, H, ws, n_blocks, eps=1e-12, normalize=True, status=None):
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_ipsdta_update_source(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
+                                                      int(bool(normalize)), ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64,
+                                                      self._st()), "assx_ipsdta_update_source")
+
+    def ipsdta_update_spatial(self, X, W, U, H, ws, n_blocks, n_sweeps=1, eps=1e-12, status=None):
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        if int(n_sweeps) < 0:
+            raise ValueError("GaussIPSDTA: n_sweeps must be >= 0, got %d" % int(n_sweeps))
+        self._check(self._L.assx_ipsdta_update_spatial(self.ctx, int(n_sweeps), ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
+                                                       ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_ipsdta_update_spatial")
+
+    def ipsdta_loss(self, X, W, U, H, ws, n_blocks, eps=1e-12, loss=None, status=None):
+        """loss (1,) float64: the negative log-likelihood of the model as it stands."""
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._ipsdta_array(loss, (1,), "loss", torch.float64)
+        self._check(self._L.assx_ipsdta_loss(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(loss), ptr(status),
+                                             ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), "assx_ipsdta_loss")
+        return loss
+
+    def ipsdta_iterate(self, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps=1e-12, normalize=True, loss=None,
+                       status=None):
+        """n_iter x (source update, `spatial_iteration` sweeps, loss); loss: (n_iter,) float64 or None."""
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
+        if int(n_iter) < 0 or int(spatial_iteration) < 0:
+            raise ValueError("GaussIPSDTA: n_iter and spatial_iteration must be >= 0, got %d and %d"
+                             % (int(n_iter), int(spatial_iteration)))
+        if loss is not None:
+            self._ipsdta_array(loss, (int(n_iter),), "loss", torch.float64)
+        self._check(self._L.assx_ipsdta_iterate(self.ctx, int(n_iter), int(spatial_iteration), ptr(X), ptr(W), ptr(U), ptr(H),
+                                                float(eps), int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), M, F, T, K,
+                                                nb, _lib.F64, self._st()), "assx_ipsdta_iterate")
+
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""
         if A.dim() != 3 or tuple(Bm.shape) != tuple(A.shape) or A.shape[1] != A.shape[2]:

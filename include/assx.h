@@ -476,6 +476,52 @@ int assx_psdtf_iterate(assx_ctx* ctx, int n_iter, const void* X, void* V, void* 
                        double* loss /* (n_iter,B) or NULL */, int32_t* status, void* ws, int B, int M, int T, int K,
                        int dtype, void* stream);
 
+/* ---- (f10) GaussIPSDTA, Kondo's block-diagonal IPSDTA (src/bss/ipsdta.py:510-688, 820-1081) ------------------------------
+ * One utterance, float64 only (ASSX_F32: ASSX_E_UNSUPPORTED).  The F bins are cut into n_blocks blocks: the first
+ * nlow = n_blocks - F % n_blocks of nn = F / n_blocks bins, the other F % n_blocks of nn + 1.  State: X (M,F,T) complex
+ * input, W (F,M,M) complex demixing filter, U (N,K,P) complex bases, H (N,K,T) activation, N = M.  A basis is PACKED: its
+ * Hermitian nb x nb blocks row-major, laid end to end in block order, P = nlow nn^2 + (n_blocks - nlow)(nn + 1)^2.
+ * Envelope (ASSX_E_ARG outside): 2 <= M <= 8, 1 <= K <= 64, 1 <= n_blocks <= F <= 2^20, largest block <= 8, T >= 1,
+ * M n_blocks T < 2^31.  `ws` (assx_ipsdta_workspace_bytes; 0 outside the envelope, no GPU needed) is scratch:
+ * 16 (2 N P T + 2 N K P + N F M^2) + 8 N n_blocks T bytes.  psd(A) is the reference's to_PSD, (A + A^H)/2 -
+ * min(lambda_min, 0) I + eps tr I; on x x^H and on y y^H + eps I the min is taken as 0.  With R = psd(sum_k H U_k) and
+ * Ri = psd(R^-1) per (source, block, frame) and y = W x:
+ *   assx_ipsdta_to_psd             psd() of n_mat Hermitian nb x nb matrices (complex, row-major), in place, 1 <= nb <= 8.
+ *   assx_ipsdta_update_basis       ipsdta.py:510-623: S_k = sum_t H Ri (y y^H + eps I) Ri, T_k = sum_t H Ri,
+ *                                  U <- psd(U S^1/2 psd(psd(psd(S^1/2 U T U S^1/2)^1/2)^-1) S^1/2 U), S^1/2 = psd(sqrt S).
+ *   assx_ipsdta_update_activation  ipsdta.py:625-688: H <- H sqrt(max(num, 0) / max(den, eps)), num = sum over the blocks of
+ *                                  Re tr(Ri U_k Ri psd(y y^H + eps I)), den of Re tr(Ri U_k).
+ *   assx_ipsdta_normalize          ipsdta.py:983-1005: U_k /= tr U_k (over all blocks), H[k,:] *= tr U_k.
+ *   assx_ipsdta_update_source      the three above in this order (the last one if `normalize`): ipsdta.py:334-345.
+ *   assx_ipsdta_update_spatial     ipsdta.py:820-975, n_sweeps times: Ri and Q[n,f] = psd(mean_t (Ri)_ii psd(x x^H)) once,
+ *                                  then per sweep, for each source and each position of a block in order, gamma, the two
+ *                                  M x M solves and the row update of W.
+ *   assx_ipsdta_loss               ipsdta.py:1015-1081: loss[0] = sum (y^H Ri y + sum log max(lambda(R), eps))
+ *                                  - 2 T sum_f log|det W_f| (|det| from an LU, its pivots floored at eps).
+ *   assx_ipsdta_iterate            n_iter x (update_source, update_spatial with `spatial_iteration` sweeps, loss into loss[i]
+ *                                  if loss != NULL), enqueued without a synchronisation, bit for bit the single calls.
+ * `status` (1,) int32 or NULL: ASSX_STATUS_SINGULAR where a block the method inverts is not positive definite or a solve
+ * meets a zero pivot (numpy.linalg raises LinAlgError there); the kernels finish either way.  No float atomics, every sum
+ * in an order fixed by the shapes. */
+size_t assx_ipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype);
+int assx_ipsdta_to_psd(assx_ctx* ctx, void* A /* (n_mat,nb,nb) complex */, int n_mat, int nb, double eps, void* stream);
+int assx_ipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* U, const void* H, double eps, int32_t* status,
+                             void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream);
+int assx_ipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps,
+                                  int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                  void* stream);
+int assx_ipsdta_normalize(assx_ctx* ctx, void* U, void* H, int M, int F, int T, int K, int n_blocks, int dtype, void* stream);
+int assx_ipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void* U, void* H, double eps, int normalize,
+                              int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream);
+int assx_ipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
+                               int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream);
+int assx_ipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U, const void* H, double eps,
+                     double* loss /* (1,) */, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                     void* stream);
+int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
+                        int normalize, double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M, int F, int T,
+                        int K, int n_blocks, int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
