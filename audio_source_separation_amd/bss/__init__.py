@@ -1,6 +1,6 @@
 """Blind source separation classes (mirror of the reference's src/bss for the HIP hot path)."""
 
-_EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta"}
+_EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta", "tIPSDTA": "ipsdta"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -1,13 +1,14 @@
-"""Independent positive semidefinite tensor analysis on MI355X -- drop-in for `bss.ipsdta.GaussIPSDTA` of the reference
-with author='Kondo' (src/bss/ipsdta.py:22-355, 510-688, 820-1081).
+"""Independent positive semidefinite tensor analysis on MI355X -- drop-in for `bss.ipsdta.GaussIPSDTA` and
+`bss.ipsdta.tIPSDTA` of the reference with author='Kondo' (src/bss/ipsdta.py:22-355, 510-688, 820-1081, 1083-1762).
 
 Same constructor and call, `ipsdta(input, iteration=100, **kwargs) -> output` for an input of shape (n_channels, n_bins,
 n_frames), the attributes `demix_filter` (n_bins, n_sources, n_channels), `basis`, `activation` (n_sources, n_basis,
 n_frames), `estimation`, `loss`, warm start through `hasattr`, callbacks before the loop and after every iteration.  `basis`
 has the reference's two layouts: one array (n_sources, n_blocks, n_neighbors, n_neighbors, n_basis) when n_blocks divides
 n_bins, the tuple (low, high) otherwise.  The MM source model, the VCD spatial model and the loss run as HIP kernels
-(include/assx.h (f10): assx_ipsdta_*); without callbacks the loop is one call of assx_ipsdta_iterate.  There is no CPU
-fallback.
+(include/assx.h (f10): assx_ipsdta_*, (f11): assx_tipsdta_* for the Student-t model); without callbacks the loop is one
+call of the model's `iterate` entry point.  There is no CPU fallback.  What the two models share lives in `_BlockDiagonalIPSDTA`, between the
+abstract `IPSDTAbase` and the models.
 
 As in the reference, the constructor overwrites its `spatial_iteration` argument with the default of 10 (ipsdta.py:186-190:
 the defaults are written after the argument, only `n_blocks` and `spatial_iteration` given as extra keywords -- which Python
@@ -125,9 +126,6 @@ class IPSDTAbase(DeviceState):
 
         return s.format(**self.__dict__)
 
-    def update_once(self):
-        raise NotImplementedError("Implement 'update_once' method.")
-
     def separate(self, input, demix_filter):
         """
         Args:
@@ -141,47 +139,34 @@ class IPSDTAbase(DeviceState):
         W = to_device(demix_filter, torch.complex128, eng.dev).unsqueeze(0)
         return to_numpy(eng.demix(X, W)[0], np.complex128)
 
+    def update_once(self):
+        raise NotImplementedError("Implement 'update_once' method.")
+
     def compute_negative_loglikelihood(self):
         raise NotImplementedError("Implement `compute_negative_loglikelihood` method.")
 
 
-class GaussIPSDTA(IPSDTAbase):
-    """reference: ipsdta.py:155-1081 with author='Kondo' ("Convergence-Guaranteed Independent Positive Semidefinite Tensor
-    Analysis Based on Student's t Distribution", ICASSP 2020, for the MM and VCD updates).  float64 / complex128, one
-    utterance, 2 <= n_channels <= 8 with n_sources = n_channels, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins, blocks of at
-    most 8 bins; anything else raises ValueError before a kernel is launched.  author='Ikeshita' (EM and fixed-point) is not
-    implemented.  A block that is not positive definite where the method inverts it raises numpy.linalg.LinAlgError at the
-    end of the call (and of the stand-alone steps), not in the middle."""
+class _BlockDiagonalIPSDTA(IPSDTAbase):
+    """What GaussIPSDTA and tIPSDTA (author='Kondo') share: the reset with its refusals, warm start, the call, the stepwise
+    methods and the fast loop.  A model names the prefix of its Engine methods (`_OPS`) and what they take beyond the Gauss
+    ones (`_model_kwargs`)."""
+    _OPS = None  # the prefix of the model's Engine methods
 
-    def __init__(self, n_basis=10, spatial_iteration=None, normalize=True, callbacks=None, reference_id=0, author='Kondo',
-                 recordable_loss=True, eps=EPS, dtype='float64', device=None, **kwargs):
-        """
-        Args:
-            n_basis <int>: Number of basis matrices
-            callbacks <callable> or <list<callable>>:
-            reference_id <int>: Reference microphone index
-            author <str>: 'Kondo' ('Ikeshita' raises NotImplementedError)
-        """
-        super().__init__(n_basis=n_basis, normalize=normalize, callbacks=callbacks, reference_id=reference_id,
-                         recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+    def _op(self, name):
+        return getattr(self._engine, self._OPS + name)
 
-        self.spatial_iteration = spatial_iteration
-        self.author = author
+    def _model_kwargs(self):
+        """what the model's Engine methods take beyond the Gauss ones"""
+        return {}
 
-        if author.lower() in __authors_ipsdta__:
-            if author.lower() == 'ikeshita':
-                raise NotImplementedError("author='Ikeshita' (EM source model, fixed-point spatial model) is not implemented "
-                                          "on the GPU; only author='Kondo' is")
-            if set(kwargs) - set(__kwargs_kondo_ipsdta__) != set():
-                raise ValueError("Invalid keywords.")
-            for key in __kwargs_kondo_ipsdta__.keys():
-                setattr(self, key, __kwargs_kondo_ipsdta__[key])
-            self.algorithm_source = 'mm'
-            self.algorithm_spatial = 'vcd'
-            for key in kwargs.keys():
-                setattr(self, key, kwargs[key])
-        else:
-            raise ValueError("Not support {}'s IPSDTA".format(author))
+    def _check_author(self):
+        if self.author.lower() == 'ikeshita':
+            raise NotImplementedError("author='Ikeshita' is not implemented on the GPU; only author='Kondo' is")
+        if self.author.lower() not in __authors_ipsdta__:
+            raise ValueError("Not support {}'s IPSDTA".format(self.author))
+
+    def _check_model(self):
+        """the model's own refusals, before a device is touched"""
 
     def __call__(self, input, iteration=100, **kwargs):
         """
@@ -204,8 +189,9 @@ class GaussIPSDTA(IPSDTAbase):
                 eng = self._engine
                 loss = eng.empty((iteration,), dtype=torch.float64) if self.recordable_loss else None
                 W, U, H = self._model()
-                eng.ipsdta_iterate(iteration, self.spatial_iteration, self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps,
-                                   normalize=self.normalize, loss=loss, status=self._status)
+                self._op("iterate")(iteration, self.spatial_iteration, self._X, W, U, H, self._ws, self.n_blocks,
+                                    eps=self.eps, normalize=self.normalize, loss=loss, status=self._status,
+                                    **self._model_kwargs())
                 self._touch("W", "U", "H")
                 if loss is not None:
                     self.loss.append_device_block(loss.unsqueeze(1), False)
@@ -233,9 +219,10 @@ class GaussIPSDTA(IPSDTAbase):
               "compute_negative_loglikelihood", "compute_negative_loglikelihood_block_diagonal")
 
     def _fast_loop_ok(self):
-        """The loop goes to assx_ipsdta_iterate when every step is this module's and `loss` is still the lazy list."""
+        """The loop goes to the model's `iterate` entry point when every step is this module's and `loss` is still the lazy
+        list."""
         cls = type(self)
-        return all(getattr(cls, n) is getattr(GaussIPSDTA, n) for n in self._STEPS) \
+        return all(getattr(cls, n) is getattr(_BlockDiagonalIPSDTA, n) for n in self._STEPS) \
             and (not self.recordable_loss or isinstance(self.loss, LazyLossList))
 
     def _append_loss(self, loss):
@@ -256,10 +243,7 @@ class GaussIPSDTA(IPSDTAbase):
         for key in kwargs.keys():
             setattr(self, key, kwargs[key])
 
-        if self.author.lower() == 'ikeshita':
-            raise NotImplementedError("author='Ikeshita' is not implemented on the GPU; only author='Kondo' is")
-        if self.author.lower() not in __authors_ipsdta__:
-            raise ValueError("Not support {}'s IPSDTA".format(self.author))
+        self._check_author()
         self._reset_block_diagonal(**kwargs)
 
     def _reset_block_diagonal(self, **kwargs):
@@ -295,6 +279,7 @@ class GaussIPSDTA(IPSDTAbase):
                 self.BLOCK_MAX, n_bins, n_blocks, n_neighbors + (n_remains > 0)))
         if not 0 <= int(self.reference_id) < n_channels:
             raise ValueError("reference_id must be in [0, {}), got {!r}".format(n_channels, self.reference_id))
+        self._check_model()
 
         self.n_sources, self.n_channels = n_sources, n_channels
         self.n_bins, self.n_frames = n_bins, n_frames
@@ -327,7 +312,7 @@ class GaussIPSDTA(IPSDTAbase):
         self.is_complex = True
         eng = self._ensure_engine()
         self._X = to_device(X, torch.complex128, eng.dev)
-        self._ws = eng.ipsdta_workspace(n_channels, n_bins, n_frames, n_basis, n_blocks)
+        self._ws = self._op("workspace")(n_channels, n_bins, n_frames, n_basis, n_blocks, **self._model_kwargs())
         self._status = eng.new_status(1)
 
         self.demix_filter = W
@@ -350,33 +335,20 @@ class GaussIPSDTA(IPSDTAbase):
         """(W (F, M, M), U (N, K, P), H (N, K, T)) on the device"""
         return self._dev("W", True)[0], self._dev("U", True)[0], self._dev("H", False)[0]
 
-    def __repr__(self):
-        s = "Gauss-IPSDTA("
-        s += "n_basis={n_basis}"
-        s += ", normalize={normalize}"
-        s += ", algorithm(source)={algorithm_source}"
-        s += ", algorithm(spatial)={algorithm_spatial}"
-        if self.author.lower() in __authors_ipsdta__:
-            s += ", n_blocks={n_blocks}"
-        s += ", author={author}"
-        s += ")"
-
-        return s.format(**self.__dict__)
-
     def update_once(self):
         self.update_source_model()
 
         cls = type(self)
-        if cls.update_spatial_model is not GaussIPSDTA.update_spatial_model \
-                or cls.update_spatial_model_vcd is not GaussIPSDTA.update_spatial_model_vcd:
+        if cls.update_spatial_model is not _BlockDiagonalIPSDTA.update_spatial_model \
+                or cls.update_spatial_model_vcd is not _BlockDiagonalIPSDTA.update_spatial_model_vcd:
             for spatial_idx in range(self.spatial_iteration):
                 self.update_spatial_model()
             return
 
-        # all sweeps in one call: R^-1 and Q depend on the source model alone and are computed once
+        # all sweeps in one call: R^-1 (and Q in the Gauss model) depend on the source model alone and are computed once
         W, U, H = self._model()
-        self._engine.ipsdta_update_spatial(self._X, W, U, H, self._ws, self.n_blocks, n_sweeps=self.spatial_iteration,
-                                           eps=self.eps, status=self._status)
+        self._op("update_spatial")(self._X, W, U, H, self._ws, self.n_blocks, n_sweeps=self.spatial_iteration, eps=self.eps,
+                                   status=self._status, **self._model_kwargs())
         self._touch("W")
 
     def update_source_model(self):
@@ -404,19 +376,21 @@ class GaussIPSDTA(IPSDTAbase):
 
     def update_basis_mm(self):
         W, U, H = self._model()
-        self._engine.ipsdta_update_basis(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status)
+        self._op("update_basis")(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status,
+                                 **self._model_kwargs())
         self._touch("U")
 
     def update_activation_mm(self):
         W, U, H = self._model()
-        self._engine.ipsdta_update_activation(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status)
+        self._op("update_activation")(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status,
+                                      **self._model_kwargs())
         self._touch("H")
 
     def update_spatial_model_vcd(self):
         """one VCD sweep"""
         W, U, H = self._model()
-        self._engine.ipsdta_update_spatial(self._X, W, U, H, self._ws, self.n_blocks, n_sweeps=1, eps=self.eps,
-                                           status=self._status)
+        self._op("update_spatial")(self._X, W, U, H, self._ws, self.n_blocks, n_sweeps=1, eps=self.eps, status=self._status,
+                                   **self._model_kwargs())
         self._touch("W")
 
     def normalize_psdtf(self):
@@ -429,7 +403,8 @@ class GaussIPSDTA(IPSDTAbase):
 
     def _loss_device(self):
         W, U, H = self._model()
-        return self._engine.ipsdta_loss(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status)
+        return self._op("loss")(self._X, W, U, H, self._ws, self.n_blocks, eps=self.eps, status=self._status,
+                                **self._model_kwargs())
 
     def compute_negative_loglikelihood(self):
         return self.compute_negative_loglikelihood_block_diagonal()
@@ -438,3 +413,118 @@ class GaussIPSDTA(IPSDTAbase):
         loss = np.float64(self._loss_device().item())
         self._check_status()
         return loss
+
+
+class GaussIPSDTA(_BlockDiagonalIPSDTA):
+    """reference: ipsdta.py:155-1081 with author='Kondo' ("Convergence-Guaranteed Independent Positive Semidefinite Tensor
+    Analysis Based on Student's t Distribution", ICASSP 2020, for the MM and VCD updates).  float64 / complex128, one
+    utterance, 2 <= n_channels <= 8 with n_sources = n_channels, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins, blocks of at
+    most 8 bins; anything else raises ValueError before a kernel is launched.  author='Ikeshita' (EM and fixed-point) is not
+    implemented.  A block that is not positive definite where the method inverts it raises numpy.linalg.LinAlgError at the
+    end of the call (and of the stand-alone steps), not in the middle."""
+    _OPS = "ipsdta_"
+
+    def __init__(self, n_basis=10, spatial_iteration=None, normalize=True, callbacks=None, reference_id=0, author='Kondo',
+                 recordable_loss=True, eps=EPS, dtype='float64', device=None, **kwargs):
+        """
+        Args:
+            n_basis <int>: Number of basis matrices
+            callbacks <callable> or <list<callable>>:
+            reference_id <int>: Reference microphone index
+            author <str>: 'Kondo' ('Ikeshita' raises NotImplementedError)
+        """
+        super().__init__(n_basis=n_basis, normalize=normalize, callbacks=callbacks, reference_id=reference_id,
+                         recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+
+        self.spatial_iteration = spatial_iteration
+        self.author = author
+
+        if author.lower() in __authors_ipsdta__:
+            if author.lower() == 'ikeshita':
+                raise NotImplementedError("author='Ikeshita' (EM source model, fixed-point spatial model) is not implemented "
+                                          "on the GPU; only author='Kondo' is")
+            if set(kwargs) - set(__kwargs_kondo_ipsdta__) != set():
+                raise ValueError("Invalid keywords.")
+            for key in __kwargs_kondo_ipsdta__.keys():
+                setattr(self, key, __kwargs_kondo_ipsdta__[key])
+            self.algorithm_source = 'mm'
+            self.algorithm_spatial = 'vcd'
+            for key in kwargs.keys():
+                setattr(self, key, kwargs[key])
+        else:
+            raise ValueError("Not support {}'s IPSDTA".format(author))
+
+    def __repr__(self):
+        s = "Gauss-IPSDTA("
+        s += "n_basis={n_basis}"
+        s += ", normalize={normalize}"
+        s += ", algorithm(source)={algorithm_source}"
+        s += ", algorithm(spatial)={algorithm_spatial}"
+        if self.author.lower() in __authors_ipsdta__:
+            s += ", n_blocks={n_blocks}"
+        s += ", author={author}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+
+class tIPSDTA(_BlockDiagonalIPSDTA):
+    """reference: ipsdta.py:1083-1762 ("Convergence-Guaranteed Independent Positive Semidefinite Tensor Analysis Based on
+    Student's t Distribution", ICASSP 2020): GaussIPSDTA's envelope, refusals and stepwise methods, with every update
+    weighted per (source, frame) through the degree of freedom `nu` (finite and > 0).  The kernels are assx_tipsdta_* of
+    include/assx.h (f11); the normalisation is the Gauss one.  Any author but 'Kondo' raises ValueError, as in the
+    reference."""
+    _OPS = "tipsdta_"
+
+    def __init__(self, n_basis=10, nu=1, spatial_iteration=None, normalize=True, callbacks=None, reference_id=0, author='Kondo',
+                 recordable_loss=True, eps=EPS, dtype='float64', device=None, **kwargs):
+        """
+        Args:
+            nu <float>: Degree of freedom
+            author <str>: 'Kondo'
+        """
+        super().__init__(n_basis=n_basis, normalize=normalize, callbacks=callbacks, reference_id=reference_id,
+                         recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+
+        self.nu = nu
+        self.spatial_iteration = spatial_iteration
+        self.author = author
+
+        if author.lower() == 'kondo':
+            if set(kwargs) - set(__kwargs_kondo_ipsdta__) != set():
+                raise ValueError("Invalid keywords.")
+            for key in __kwargs_kondo_ipsdta__.keys():
+                setattr(self, key, __kwargs_kondo_ipsdta__[key])
+            self.algorithm_source = 'mm'
+            self.algorithm_spatial = 'vcd'
+        else:
+            raise ValueError("Not support {}'s IPSDTA".format(author))
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+    def _model_kwargs(self):
+        return {"nu": float(self.nu)}
+
+    def _check_author(self):
+        if self.author.lower() != 'kondo':
+            raise ValueError("Not support {}'s IPSDTA".format(self.author))
+
+    def _check_model(self):
+        nu = self.nu
+        if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)) or not 0 < nu < np.inf:
+            raise ValueError("nu must be a finite number > 0, got {!r}".format(nu))
+
+    def __repr__(self):
+        s = "t-IPSDTA("
+        s += "n_basis={n_basis}"
+        s += ", nu={nu}"
+        s += ", normalize={normalize}"
+        s += ", algorithm(source)={algorithm_source}"
+        s += ", algorithm(spatial)={algorithm_spatial}"
+        if self.author.lower() in __authors_ipsdta__:
+            s += ", n_blocks={n_blocks}"
+        s += ", author={author}"
+        s += ")"
+
+        return s.format(**self.__dict__)

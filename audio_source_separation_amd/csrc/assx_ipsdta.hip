@@ -29,6 +29,10 @@
 // of y y^H + eps I.  A block that is not positive definite where the method inverts it, or a singular solve, sets
 // ASSX_STATUS_SINGULAR; the kernels finish either way.  No float atomics, no partition that depends on anything but the
 // shapes, every sum in a fixed order.
+//
+// tIPSDTA, the Student-t model of the same paper series (src/bss/ipsdta.py:1083-1762), shares the model, contraction, basis,
+// activation and normalisation kernels (the template flag TD switches its weights in; the Gauss instantiations are
+// unchanged) and adds ip_pi_kernel, ip_tstep_kernel and ip_tloss_kernel, described where they are defined.
 #include "assx_common.hpp"
 #include "assx_herm_linalg.hpp"
 
@@ -228,13 +232,14 @@ __device__ __forceinline__ void ip_flag(int32_t* status, bool bad) {
 
 enum { MODE_BASIS = 0, MODE_ACT = 1, MODE_SPATIAL = 2, MODE_LOSS = 3 };
 
-// blocks b0 .. b0 + nbk - 1, all of size NB
-template <int NB, int MODE>
+// blocks b0 .. b0 + nbk - 1, all of size NB.  TD (the Student-t model): q = y^H Ri y goes to qb (N,n_blocks,T) in every
+// mode but SPATIAL, and LOSS writes sum log max(lambda(R), eps) alone
+template <int NB, int MODE, bool TD = false>
 __global__ void __launch_bounds__(BLK) ip_model_kernel(const cx* __restrict__ X, const cx* __restrict__ W,
                                                        const cx* __restrict__ U, const double* __restrict__ H,
                                                        cx* __restrict__ ri, cx* __restrict__ zz,
                                                        double* __restrict__ lossp, int32_t* status, double eps, IpGeo g,
-                                                       int b0, int nbk) {
+                                                       int b0, int nbk, double* __restrict__ qb = nullptr) {
   const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x;
   const size_t T = g.T;
   if (idx >= (size_t)g.M * nbk * T) return;
@@ -288,7 +293,16 @@ __global__ void __launch_bounds__(BLK) ip_model_kernel(const cx* __restrict__ X,
     }
     vr[i] = sr, vi[i] = si;
   }
-  if (MODE == MODE_LOSS) {
+  if (TD && MODE != MODE_SPATIAL) {  // the spatial update forms q per sweep (ip_tq_kernel)
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) q += yr[i] * vr[i] + yi[i] * vi[i];
+    qb[((size_t)n * g.nblk + b) * T + t] = q;
+    if (MODE == MODE_LOSS) {
+      lossp[((size_t)n * g.nblk + b) * T + t] = ld;
+      return;
+    }
+  } else if (MODE == MODE_LOSS) {
     double q = 0.0;
 #pragma unroll
     for (int i = 0; i < NB; ++i) q += yr[i] * vr[i] + yi[i] * vi[i];
@@ -318,9 +332,12 @@ __global__ void __launch_bounds__(BLK) ip_model_kernel(const cx* __restrict__ X,
   }
 }
 
-// one wave per (source, entry): part[n][0][k][e] = sum_t H[n,k,t] zz[n,e,t], part[n][1][k][e] the same with ri
+// one wave per (source, entry): part[n][0][k][e] = sum_t H[n,k,t] zz[n,e,t], part[n][1][k][e] the same with ri.  TD: zz is
+// weighted by pi[n,t] first
+template <bool TD = false>
 __global__ void __launch_bounds__(BLK) ip_contract_kernel(const double* __restrict__ H, const cx* __restrict__ ri,
-                                                          const cx* __restrict__ zz, cx* __restrict__ part, IpGeo g) {
+                                                          const cx* __restrict__ zz, cx* __restrict__ part, IpGeo g,
+                                                          const double* __restrict__ pi = nullptr) {
   const size_t wv = (size_t)blockIdx.x * NW + threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
   if (wv >= (size_t)g.M * g.P) return;
@@ -331,7 +348,12 @@ __global__ void __launch_bounds__(BLK) ip_contract_kernel(const double* __restri
 #pragma unroll
     for (int c = 0; c < KC; ++c) s[c][0] = s[c][1] = r[c][0] = r[c][1] = 0.0;
     for (size_t t = lane; t < T; t += WAVE) {
-      const cx z = zrow[t], q = rrow[t];
+      cx z = zrow[t];
+      const cx q = rrow[t];
+      if (TD) {
+        const double p = pi[n * T + t];
+        z.x = p * z.x, z.y = p * z.y;
+      }
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
         const double h = H[(n * g.K + min(k0 + c, g.K - 1)) * T + t];
@@ -385,10 +407,11 @@ __global__ void __launch_bounds__(BLK) ip_basis_kernel(cx* __restrict__ U, const
   ip_store(C, Up);
 }
 
-// G in zz, Ri in ri (both from the new U)
+// G in zz, Ri in ri (both from the new U).  TD: num is weighted by pi[n,t] before its floor
+template <bool TD = false>
 __global__ void __launch_bounds__(BLK) ip_act_kernel(const cx* __restrict__ U, double* __restrict__ H,
                                                      const cx* __restrict__ ri, const cx* __restrict__ zz, double eps,
-                                                     IpGeo g) {
+                                                     IpGeo g, const double* __restrict__ pi = nullptr) {
   const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x, T = g.T;
   if (idx >= (size_t)g.M * g.K * T) return;
   const size_t t = idx % T, nk = idx / T, n = nk / g.K;
@@ -399,6 +422,7 @@ __global__ void __launch_bounds__(BLK) ip_act_kernel(const cx* __restrict__ U, d
     num += u.x * z.x + u.y * z.y;
     den += u.x * r.x + u.y * r.y;
   }
+  if (TD) num = pi[n * T + t] * num;
   H[idx] = H[idx] * sqrt(fmax(num, 0.0) / fmax(den, eps));
 }
 
@@ -617,14 +641,8 @@ __global__ void __launch_bounds__(BLK) ip_sweep_kernel(const cx* __restrict__ X,
   for (int e = tid; e < nb * M * M; e += BLK) W[(size_t)bk.f0 * M * M + e] = Wl[e / (M * M)][(e / M) % M][e % M];
 }
 
-// loss = sum lossp - 2 T sum_f log max(|det W_f|, ...) with |det| from an LU: sum_i log max(|u_ii|, eps)
-__global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, const double* __restrict__ lossp,
-                                                      double* __restrict__ loss, double eps, IpGeo g) {
-  __shared__ double red[NW];
-  const size_t n_terms = (size_t)g.M * g.nblk * g.T;
-  double v = 0.0;
-  for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += lossp[e];
-  v = ip_block_sum(v, red);
+// sum over the bins f = tid, tid + BLK, ... of log|det W_f| with |det| from an LU: sum_i log max(|u_ii|, eps)
+__device__ inline double ip_logdet_w(const cx* __restrict__ W, double eps, const IpGeo& g) {
   double ldw = 0.0;
   const int M = g.M;
   for (int f = threadIdx.x; f < g.F; f += BLK) {
@@ -655,7 +673,18 @@ __global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, 
         }
     }
   }
-  ldw = ip_block_sum(ldw, red);
+  return ldw;
+}
+
+// loss = sum lossp - 2 T sum_f log max(|det W_f|, ...)
+__global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, const double* __restrict__ lossp,
+                                                      double* __restrict__ loss, double eps, IpGeo g) {
+  __shared__ double red[NW];
+  const size_t n_terms = (size_t)g.M * g.nblk * g.T;
+  double v = 0.0;
+  for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += lossp[e];
+  v = ip_block_sum(v, red);
+  const double ldw = ip_block_sum(ip_logdet_w(W, eps, g), red);
   if (threadIdx.x == 0) loss[0] = v - 2.0 * (double)g.T * ldw;
 }
 
@@ -682,26 +711,30 @@ struct IpArgs {
   char* ws;
   IpGeo g;
   hipStream_t st;
+  double nu;  // the Student-t entry points only
 };
 
 inline unsigned ip_grid(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
 
 // the model kernel over the low blocks, then over the high ones
-template <int MODE>
-int ip_model(assx_ctx* ctx, const IpArgs& a) {
+template <int MODE, bool TD>
+int ip_model_at(assx_ctx* ctx, const IpArgs& a, cx* ri, cx* zz, double* lossp, double* qb) {
   const IpGeo& g = a.g;
-  const IpLayout L = ip_layout(g);
-  cx *ri = (cx*)(a.ws + L.ri), *zz = (cx*)(a.ws + L.zz);
-  double* lossp = (double*)(a.ws + L.lossp);
   for (int part = 0; part < 2; ++part) {
     const int b0 = part ? g.nlow : 0, nbk = part ? g.nblk - g.nlow : g.nlow, nb = g.nn + part;
     if (nbk == 0) continue;
-    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_model_kernel<NB, MODE>), dim3(ip_grid((size_t)g.M * nbk * g.T)), dim3(BLK), 0,
-                                        a.st, a.X, (const cx*)a.W, (const cx*)a.U, (const double*)a.H, ri, zz, lossp,
-                                        a.status, a.eps, g, b0, nbk));
+    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_model_kernel<NB, MODE, TD>), dim3(ip_grid((size_t)g.M * nbk * g.T)), dim3(BLK),
+                                        0, a.st, a.X, (const cx*)a.W, (const cx*)a.U, (const double*)a.H, ri, zz, lossp,
+                                        a.status, a.eps, g, b0, nbk, qb));
     ASSX_LAUNCH_CHECK(ctx, "ip_model_kernel");
   }
   return 0;
+}
+
+template <int MODE>
+int ip_model(assx_ctx* ctx, const IpArgs& a) {
+  const IpLayout L = ip_layout(a.g);
+  return ip_model_at<MODE, false>(ctx, a, (cx*)(a.ws + L.ri), (cx*)(a.ws + L.zz), (double*)(a.ws + L.lossp), nullptr);
 }
 
 int ip_update_basis(assx_ctx* ctx, const IpArgs& a) {
@@ -711,7 +744,7 @@ int ip_update_basis(assx_ctx* ctx, const IpArgs& a) {
   int rc = ip_model<MODE_BASIS>(ctx, a);
   if (rc) return rc;
   const size_t waves = (size_t)g.M * g.P;
-  hipLaunchKernelGGL(ip_contract_kernel, dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st, (const double*)a.H,
+  hipLaunchKernelGGL((ip_contract_kernel<false>), dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st, (const double*)a.H,
                      (const cx*)ri, (const cx*)zz, part, g);
   ASSX_LAUNCH_CHECK(ctx, "ip_contract_kernel");
   for (int p = 0; p < 2; ++p) {
@@ -729,7 +762,7 @@ int ip_update_activation(assx_ctx* ctx, const IpArgs& a) {
   const IpLayout L = ip_layout(g);
   int rc = ip_model<MODE_ACT>(ctx, a);
   if (rc) return rc;
-  hipLaunchKernelGGL(ip_act_kernel, dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
+  hipLaunchKernelGGL((ip_act_kernel<false>), dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
                      (const cx*)(a.ws + L.ri), (const cx*)(a.ws + L.zz), a.eps, g);
   ASSX_LAUNCH_CHECK(ctx, "ip_act_kernel");
   return 0;
@@ -790,6 +823,356 @@ int ip_args(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, 
                M, F, T, K, n_blocks);
   a.X = (const cx*)X, a.W = (cx*)W, a.U = (cx*)U, a.H = (double*)H, a.eps = eps, a.status = status, a.ws = (char*)ws;
   a.st = (hipStream_t)stream;
+  return 0;
+}
+
+// ---- the Student-t model (tIPSDTA, src/bss/ipsdta.py:1083-1762) --------------------------------------------------------
+// Every update is weighted per (source, frame) by pi[n,t] = (nu + 2 F) / (nu + 2 sum_b q[n,b,t]), q = y_b^H Ri_b y_b.  The
+// model pass writes q per block (TD above), ip_pi_kernel adds the blocks in index order.  The source model weights S_k and
+// num by pi.  The spatial model cannot hoist Q (it holds pi, which holds W): a sweep is the sequence of steps (source n;
+// the low blocks at position 0..nn-1, then the high blocks at position 0..nn), each step ip_pi_kernel for source n and then
+// ip_tstep_kernel over the blocks of the group; stream order between the two is the only coupling between blocks.  A sweep
+// starts with ip_tq_kernel, which forms q of all blocks from the current W.
+
+// ri, zz: (N,P,T) complex; part: (N,2,K,P) complex; qb, ld: (N,n_blocks,T) double; pi: (N,T) double
+struct IpTLayout {
+  size_t ri, zz, part, qb, ld, pi, total;
+};
+
+IpTLayout ip_tlayout(const IpGeo& g) {
+  const size_t c = sizeof(cx), N = g.M;
+  IpTLayout L;
+  L.ri = 0;
+  L.zz = L.ri + N * g.P * g.T * c;
+  L.part = L.zz + N * g.P * g.T * c;
+  L.qb = L.part + N * 2 * g.K * g.P * c;
+  L.ld = L.qb + N * g.nblk * g.T * sizeof(double);
+  L.pi = L.ld + N * g.nblk * g.T * sizeof(double);
+  L.total = L.pi + N * g.T * sizeof(double);
+  return L;
+}
+
+// one thread per (source, frame) of the sources n0 .. n0 + cnt - 1, the blocks in index order
+__global__ void __launch_bounds__(BLK) ip_pi_kernel(const double* __restrict__ qb, double* __restrict__ pi, double nu, IpGeo g,
+                                                    int n0, int cnt) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x, T = g.T;
+  if (idx >= (size_t)cnt * T) return;
+  const size_t n = n0 + idx / T, t = idx % T;
+  double s = 0.0;
+  for (int b = 0; b < g.nblk; ++b) s += qb[(n * g.nblk + b) * T + t];
+  pi[n * T + t] = (nu + 2.0 * (double)g.F) / (nu + 2.0 * s);
+}
+
+// q[n,b,t] = y_b^H Ri_b y_b from the Ri of the workspace and the current W, one thread per (source, block, frame).  Every
+// sweep starts from this kernel's q, whether it is the first of its call or not: a call of n sweeps equals n calls of one
+// bit for bit (the step kernel's own q serves the steps after it within the sweep).
+__global__ void __launch_bounds__(BLK) ip_tq_kernel(const cx* __restrict__ X, const cx* __restrict__ W,
+                                                    const cx* __restrict__ ri, double* __restrict__ qb, IpGeo g) {
+  const size_t idx = (size_t)blockIdx.x * BLK + threadIdx.x, T = g.T;
+  if (idx >= (size_t)g.M * g.nblk * T) return;
+  const size_t t = idx % T;
+  const int b = (int)((idx / T) % g.nblk), n = (int)(idx / (T * g.nblk));
+  const IpBlock bk = ip_block(g, b);
+  const int nb = bk.nb;
+  const cx* rn = ri + ((size_t)n * g.P + bk.off) * T;
+  double yr[NBMAX], yi[NBMAX];
+#pragma unroll
+  for (int j = 0; j < NBMAX; ++j) {
+    cx y = make_double2(0.0, 0.0);
+    if (j < nb) {
+      for (int c = 0; c < g.M; ++c) {
+        const cx m = cmul(W[((size_t)(bk.f0 + j) * g.M + n) * g.M + c], X[((size_t)c * g.F + bk.f0 + j) * T + t]);
+        y.x += m.x, y.y += m.y;
+      }
+    }
+    yr[j] = y.x, yi[j] = y.y;
+  }
+  double q = 0.0;
+#pragma unroll
+  for (int a = 0; a < NBMAX; ++a) {
+    if (a < nb) {
+      double sr = 0.0, si = 0.0;
+#pragma unroll
+      for (int j = 0; j < NBMAX; ++j) {
+        if (j < nb) {
+          const cx r = rn[(size_t)(a * nb + j) * T + t];
+          sr += r.x * yr[j] - r.y * yi[j];
+          si += r.x * yi[j] + r.y * yr[j];
+        }
+      }
+      q += yr[a] * sr + yi[a] * si;
+    }
+  }
+  qb[idx] = q;
+}
+
+// One VCD step of source n at position i of the blocks b0 + blockIdx.x (all of one size): over the frames, the Hermitian
+// Q = mean_t pi (Ri)_ii (x x^H + eps |x|^2 I) (its diagonal and the entries below it, M^2 doubles) and gamma = mean_t pi
+// sum_{j != i} (Ri)_ji x conj(y_j) (2 M doubles) per thread, a butterfly and LDS add them in a fixed order; thread 0 applies
+// psd, solves and writes row n of W_f; then all threads recompute q[n,b,:] with the new row.
+template <int M>
+__global__ void __launch_bounds__(BLK) ip_tstep_kernel(const cx* __restrict__ X, cx* __restrict__ W, const cx* __restrict__ ri,
+                                                       const double* __restrict__ pi, double* __restrict__ qb,
+                                                       int32_t* status, double eps, IpGeo g, int n, int b0, int i) {
+  constexpr int NQ = M * M, NA = NQ + 2 * M;
+  static_assert(NW == 4, "the waves' partial sums are added as ((0 + 1) + 2) + 3");
+  __shared__ cx Wf[MMAX][MMAX];
+  __shared__ cx wn[NBMAX][MMAX];
+  __shared__ double red[NW][NA];
+  __shared__ cx Qs[M * M];
+  __shared__ cx gam[MMAX];
+  const int b = b0 + blockIdx.x, tid = threadIdx.x;
+  const IpBlock bk = ip_block(g, b);
+  const int nb = bk.nb, f = bk.f0 + i;
+  const size_t T = g.T;
+  for (int e = tid; e < M * M; e += BLK) Wf[e / M][e % M] = W[(size_t)f * M * M + e];
+  for (int e = tid; e < nb * M; e += BLK) wn[e / M][e % M] = W[((size_t)(bk.f0 + e / M) * M + n) * M + e % M];
+  __syncthreads();
+  const double* pin = pi + (size_t)n * T;
+  const cx* rn = ri + ((size_t)n * g.P + bk.off) * T;
+  double acc[NA];
+#pragma unroll
+  for (int k = 0; k < NA; ++k) acc[k] = 0.0;
+  for (size_t t = tid; t < T; t += BLK) {
+    const double p = pin[t];
+    cx x[M];
+    double tr = 0.0;
+#pragma unroll
+    for (int c = 0; c < M; ++c) {
+      x[c] = X[((size_t)c * g.F + f) * T + t];
+      tr += x[c].x * x[c].x + x[c].y * x[c].y;
+    }
+    const double wt = p * rn[(size_t)(i * nb + i) * T + t].x;
+    int k = 0;
+#pragma unroll
+    for (int c = 0; c < M; ++c)
+#pragma unroll
+      for (int d = 0; d <= c; ++d) {
+        double pr = x[c].x * x[d].x + x[c].y * x[d].y;
+        if (c == d) {
+          pr += eps * tr;
+          acc[k++] += wt * pr;
+        } else {
+          acc[k++] += wt * pr;
+          acc[k++] += wt * (x[c].y * x[d].x - x[c].x * x[d].y);
+        }
+      }
+    if (nb > 1) {
+      cx s = make_double2(0.0, 0.0);
+      for (int j = 0; j < nb; ++j) {
+        if (j == i) continue;
+        cx y = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int c = 0; c < M; ++c) {
+          const cx m = cmul(wn[j][c], X[((size_t)c * g.F + bk.f0 + j) * T + t]);
+          y.x += m.x, y.y += m.y;
+        }
+        const cx m = cmulc(rn[(size_t)(j * nb + i) * T + t], y);
+        s.x += m.x, s.y += m.y;
+      }
+      s.x = p * s.x, s.y = p * s.y;
+#pragma unroll
+      for (int c = 0; c < M; ++c) {
+        const cx m = cmul(s, x[c]);
+        acc[NQ + 2 * c] += m.x, acc[NQ + 2 * c + 1] += m.y;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NA; ++k) {
+    for (int o = WAVE / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+    if ((tid & (WAVE - 1)) == 0) red[tid / WAVE][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double tot[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) tot[k] = (((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]) / (double)g.T;
+    Mat<M> Q;
+    int k = 0;
+#pragma unroll
+    for (int c = 0; c < M; ++c)
+#pragma unroll
+      for (int d = 0; d <= c; ++d) {
+        if (c == d) {
+          Q.re[c][c] = tot[k++], Q.im[c][c] = 0.0;
+        } else {
+          Q.re[c][d] = tot[k], Q.re[d][c] = tot[k++];
+          Q.im[c][d] = tot[k], Q.im[d][c] = -tot[k++];
+        }
+      }
+    ip_psd(Q, eps);
+    ip_store(Q, Qs);
+#pragma unroll
+    for (int c = 0; c < M; ++c) gam[c] = make_double2(tot[NQ + 2 * c], tot[NQ + 2 * c + 1]);
+    const bool ok = ip_vcd_row(M, n, Wf, Qs, gam, eps);
+    ip_flag(status, !ok);
+    for (int c = 0; c < M; ++c) {
+      W[((size_t)f * M + n) * M + c] = Wf[n][c];
+      wn[i][c] = Wf[n][c];
+    }
+  }
+  __syncthreads();
+  for (size_t t = tid; t < T; t += BLK) {
+    double yr[NBMAX], yi[NBMAX];
+#pragma unroll
+    for (int j = 0; j < NBMAX; ++j) {
+      cx y = make_double2(0.0, 0.0);
+      if (j < nb) {
+#pragma unroll
+        for (int c = 0; c < M; ++c) {
+          const cx m = cmul(wn[j][c], X[((size_t)c * g.F + bk.f0 + j) * T + t]);
+          y.x += m.x, y.y += m.y;
+        }
+      }
+      yr[j] = y.x, yi[j] = y.y;
+    }
+    double q = 0.0;
+#pragma unroll
+    for (int a = 0; a < NBMAX; ++a) {
+      if (a < nb) {
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int j = 0; j < NBMAX; ++j) {
+          if (j < nb) {
+            const cx r = rn[(size_t)(a * nb + j) * T + t];
+            sr += r.x * yr[j] - r.y * yi[j];
+            si += r.x * yi[j] + r.y * yr[j];
+          }
+        }
+        q += yr[a] * sr + yi[a] * si;
+      }
+    }
+    qb[((size_t)n * g.nblk + b) * T + t] = q;
+  }
+}
+
+// loss = sum ld + (nu + 2 F)/2 sum_{n,t} log(1 + (2/nu) sum_b q) - 2 T sum_f log|det W_f|, every sum in index order per thread
+__global__ void __launch_bounds__(BLK) ip_tloss_kernel(const cx* __restrict__ W, const double* __restrict__ ld,
+                                                       const double* __restrict__ qb, double* __restrict__ loss, double nu,
+                                                       double eps, IpGeo g) {
+  __shared__ double red[NW];
+  const size_t n_terms = (size_t)g.M * g.nblk * g.T, T = g.T;
+  double v = 0.0;
+  for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += ld[e];
+  v = ip_block_sum(v, red);
+  double u = 0.0;
+  for (size_t e = threadIdx.x; e < (size_t)g.M * T; e += BLK) {
+    const size_t n = e / T, t = e % T;
+    double s = 0.0;
+    for (int b = 0; b < g.nblk; ++b) s += qb[(n * g.nblk + b) * T + t];
+    u += log(1.0 + (2.0 / nu) * s);
+  }
+  u = ip_block_sum(u, red);
+  const double ldw = ip_block_sum(ip_logdet_w(W, eps, g), red);
+  if (threadIdx.x == 0) loss[0] = (v + 0.5 * (nu + 2.0 * (double)g.F) * u) - 2.0 * (double)g.T * ldw;
+}
+
+struct IpTPtrs {
+  cx *ri, *zz, *part;
+  double *qb, *ld, *pi;
+};
+
+inline IpTPtrs ip_tptrs(const IpArgs& a) {
+  const IpTLayout L = ip_tlayout(a.g);
+  return {(cx*)(a.ws + L.ri), (cx*)(a.ws + L.zz), (cx*)(a.ws + L.part), (double*)(a.ws + L.qb), (double*)(a.ws + L.ld),
+          (double*)(a.ws + L.pi)};
+}
+
+int ip_tpi(assx_ctx* ctx, const IpArgs& a, const IpTPtrs& p, int n0, int cnt) {
+  hipLaunchKernelGGL(ip_pi_kernel, dim3(ip_grid((size_t)cnt * a.g.T)), dim3(BLK), 0, a.st, (const double*)p.qb, p.pi, a.nu,
+                     a.g, n0, cnt);
+  ASSX_LAUNCH_CHECK(ctx, "ip_pi_kernel");
+  return 0;
+}
+
+int ip_tupdate_basis(assx_ctx* ctx, const IpArgs& a) {
+  const IpGeo& g = a.g;
+  const IpTPtrs p = ip_tptrs(a);
+  int rc = ip_model_at<MODE_BASIS, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  if (rc) return rc;
+  rc = ip_tpi(ctx, a, p, 0, g.M);
+  if (rc) return rc;
+  const size_t waves = (size_t)g.M * g.P;
+  hipLaunchKernelGGL((ip_contract_kernel<true>), dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st,
+                     (const double*)a.H, (const cx*)p.ri, (const cx*)p.zz, p.part, g, (const double*)p.pi);
+  ASSX_LAUNCH_CHECK(ctx, "ip_contract_kernel");
+  for (int h = 0; h < 2; ++h) {
+    const int b0 = h ? g.nlow : 0, nbk = h ? g.nblk - g.nlow : g.nlow, nb = g.nn + h;
+    if (nbk == 0) continue;
+    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_basis_kernel<NB>), dim3(ip_grid((size_t)g.M * g.K * nbk)), dim3(BLK), 0, a.st,
+                                        a.U, (const cx*)p.part, a.status, a.eps, g, b0, nbk));
+    ASSX_LAUNCH_CHECK(ctx, "ip_basis_kernel");
+  }
+  return 0;
+}
+
+int ip_tupdate_activation(assx_ctx* ctx, const IpArgs& a) {
+  const IpGeo& g = a.g;
+  const IpTPtrs p = ip_tptrs(a);
+  int rc = ip_model_at<MODE_ACT, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  if (rc) return rc;
+  rc = ip_tpi(ctx, a, p, 0, g.M);
+  if (rc) return rc;
+  hipLaunchKernelGGL((ip_act_kernel<true>), dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
+                     (const cx*)p.ri, (const cx*)p.zz, a.eps, g, (const double*)p.pi);
+  ASSX_LAUNCH_CHECK(ctx, "ip_act_kernel");
+  return 0;
+}
+
+int ip_tupdate_source(assx_ctx* ctx, const IpArgs& a, int normalize) {
+  int rc = ip_tupdate_basis(ctx, a);
+  if (rc) return rc;
+  rc = ip_tupdate_activation(ctx, a);
+  if (rc) return rc;
+  return normalize ? ip_normalize(ctx, a) : 0;
+}
+
+// 1 or 2 model launches, then per sweep the q pass and N (nn + (nn + 1 if there are high blocks)) steps of 2 launches
+int ip_tupdate_spatial(assx_ctx* ctx, const IpArgs& a, int n_sweeps) {
+  if (n_sweeps <= 0) return 0;
+  const IpGeo& g = a.g;
+  const IpTPtrs p = ip_tptrs(a);
+  int rc = ip_model_at<MODE_SPATIAL, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  if (rc) return rc;
+  for (int s = 0; s < n_sweeps; ++s) {
+    hipLaunchKernelGGL(ip_tq_kernel, dim3(ip_grid((size_t)g.M * g.nblk * g.T)), dim3(BLK), 0, a.st, a.X, (const cx*)a.W,
+                       (const cx*)p.ri, p.qb, g);
+    ASSX_LAUNCH_CHECK(ctx, "ip_tq_kernel");
+    for (int n = 0; n < g.M; ++n)
+      for (int h = 0; h < 2; ++h) {
+        const int b0 = h ? g.nlow : 0, nbk = h ? g.nblk - g.nlow : g.nlow, nb = g.nn + h;
+        if (nbk == 0) continue;
+        for (int i = 0; i < nb; ++i) {
+          rc = ip_tpi(ctx, a, p, n, 1);
+          if (rc) return rc;
+          IP_NB_SWITCH(g.M, hipLaunchKernelGGL((ip_tstep_kernel<NB>), dim3((unsigned)nbk), dim3(BLK), 0, a.st, a.X, a.W,
+                                               (const cx*)p.ri, (const double*)p.pi, p.qb, a.status, a.eps, g, n, b0, i));
+          ASSX_LAUNCH_CHECK(ctx, "ip_tstep_kernel");
+        }
+      }
+  }
+  return 0;
+}
+
+int ip_tloss(assx_ctx* ctx, const IpArgs& a, double* loss) {
+  const IpTPtrs p = ip_tptrs(a);
+  int rc = ip_model_at<MODE_LOSS, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ip_tloss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)p.ld, (const double*)p.qb,
+                     loss, a.nu, a.eps, a.g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_tloss_kernel");
+  return 0;
+}
+
+inline bool ip_nu_ok(double nu) { return nu > 0.0 && nu <= 1.7976931348623157e308; }
+
+int ip_targs(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, double eps, double nu, int32_t* status,
+             void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  int rc = ip_args(ctx, a, X, W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, ip_nu_ok(nu), ASSX_E_ARG, "tIPSDTA: nu = %g (finite and > 0)", nu);
+  a.nu = nu;
   return 0;
 }
 
@@ -885,6 +1268,84 @@ int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const 
     if (rc) return rc;
     if (loss) {
       rc = ip_loss(ctx, a, loss + it);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
+size_t assx_tipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype, double nu) {
+  IpGeo g;
+  if (dtype != ASSX_F64 || !ip_nu_ok(nu) || !ip_geo(M, F, T, K, n_blocks, g)) return 0;
+  return ip_tlayout(g).total;
+}
+
+int assx_tipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* U, const void* H, double eps, double nu,
+                              int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, (void*)W, U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_basis: NULL array");
+  return ip_tupdate_basis(ctx, a);
+}
+
+int assx_tipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps, double nu,
+                                   int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                   void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, (void*)W, (void*)U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_activation: NULL array");
+  return ip_tupdate_activation(ctx, a);
+}
+
+int assx_tipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void* U, void* H, double eps, double nu,
+                               int normalize, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                               void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, (void*)W, U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_source: NULL array");
+  return ip_tupdate_source(ctx, a, normalize);
+}
+
+int assx_tipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
+                                double nu, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, W, (void*)U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, n_sweeps >= 0, ASSX_E_ARG, "assx_tipsdta_update_spatial: n_sweeps = %d", n_sweeps);
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_spatial: NULL array");
+  return ip_tupdate_spatial(ctx, a, n_sweeps);
+}
+
+int assx_tipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U, const void* H, double eps, double nu,
+                      double* loss, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                      void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, (void*)W, (void*)U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, X && W && U && H && loss && ws, ASSX_E_NULL, "assx_tipsdta_loss: NULL array");
+  return ip_tloss(ctx, a, loss);
+}
+
+int assx_tipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
+                         double nu, int normalize, double* loss, int32_t* status, void* ws, int M, int F, int T, int K,
+                         int n_blocks, int dtype, void* stream) {
+  IpArgs a;
+  int rc = ip_targs(ctx, a, X, W, U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  if (rc) return rc;
+  ASSX_REQUIRE(ctx, n_iter >= 0 && spatial_iteration >= 0, ASSX_E_ARG,
+               "assx_tipsdta_iterate: n_iter = %d, spatial_iteration = %d", n_iter, spatial_iteration);
+  ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_iterate: NULL array");
+  for (int it = 0; it < n_iter; ++it) {
+    rc = ip_tupdate_source(ctx, a, normalize);
+    if (rc) return rc;
+    rc = ip_tupdate_spatial(ctx, a, spatial_iteration);
+    if (rc) return rc;
+    if (loss) {
+      rc = ip_tloss(ctx, a, loss + it);
       if (rc) return rc;
     }
   }

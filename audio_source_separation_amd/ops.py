@@ -814,40 +814,40 @@ class Engine:
         nn, rem = F // n_blocks, F % n_blocks
         return (n_blocks - rem) * nn * nn + rem * (nn + 1) * (nn + 1)
 
-    def _ipsdta_array(self, a, shape, name, dtype):
+    def _ipsdta_array(self, a, shape, name, dtype, model="GaussIPSDTA"):
         if a.dtype != dtype or a.device != self.dev:
-            raise ValueError("GaussIPSDTA: %s must be %s on %s, got %s on %s" % (name, dtype, self.dev, a.dtype, a.device))
+            raise ValueError("%s: %s must be %s on %s, got %s on %s" % (model, name, dtype, self.dev, a.dtype, a.device))
         if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
-            raise ValueError("GaussIPSDTA: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
+            raise ValueError("%s: %s has shape %s, needs %s (contiguous)" % (model, name, tuple(a.shape), tuple(shape)))
 
-    def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None):
+    def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None, model="GaussIPSDTA"):
         """Shapes are checked here, where they are still known: the C-ABI takes pointers and sizes."""
         if U.dim() != 3 or H.dim() != 3:
-            raise ValueError("GaussIPSDTA: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
-                             % (tuple(U.shape), tuple(H.shape)))
+            raise ValueError("%s: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
+                             % (model, tuple(U.shape), tuple(H.shape)))
         M, K, T = (int(d) for d in H.shape)
         if X is not None:
             F = int(X.shape[1])
         elif W is not None:
             F = int(W.shape[0])
         else:
-            raise ValueError("GaussIPSDTA: the number of bins is unknown without X or W")
+            raise ValueError("%s: the number of bins is unknown without X or W" % model)
         n_blocks = int(n_blocks)
         need = self._L.assx_ipsdta_workspace_bytes(M, F, T, K, n_blocks, self.prec.code)
         if need == 0:
-            raise ValueError("GaussIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
+            raise ValueError("%s supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
                              "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
-                             "n_blocks=%d" % (self.prec.name, M, F, T, K, n_blocks))
-        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, n_blocks)), "basis", torch.complex128)
-        self._ipsdta_array(H, (M, K, T), "activation", torch.float64)
+                             "n_blocks=%d" % (model, self.prec.name, M, F, T, K, n_blocks))
+        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, n_blocks)), "basis", torch.complex128, model)
+        self._ipsdta_array(H, (M, K, T), "activation", torch.float64, model)
         if X is not None:
-            self._ipsdta_array(X, (M, F, T), "input", torch.complex128)
+            self._ipsdta_array(X, (M, F, T), "input", torch.complex128, model)
         if W is not None:
-            self._ipsdta_array(W, (F, M, M), "demix_filter", torch.complex128)
+            self._ipsdta_array(W, (F, M, M), "demix_filter", torch.complex128, model)
         if ws is not None and (ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need):
-            raise ValueError("GaussIPSDTA: workspace of %d bytes, %d needed" % (ws.numel(), need))
+            raise ValueError("%s: workspace of %d bytes, %d needed" % (model, ws.numel(), need))
         if status is not None:
-            self._ipsdta_array(status, (1,), "status", torch.int32)
+            self._ipsdta_array(status, (1,), "status", torch.int32, model)
         return M, F, T, K, n_blocks
 
     def ipsdta_workspace(self, M, F, T, K, n_blocks):
@@ -926,6 +926,74 @@ class Engine:
         self._check(self._L.assx_ipsdta_iterate(self.ctx, int(n_iter), int(spatial_iteration), ptr(X), ptr(W), ptr(U), ptr(H),
                                                 float(eps), int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), M, F, T, K,
                                                 nb, _lib.F64, self._st()), "assx_ipsdta_iterate")
+
+    # ------------------------------------------------------------------ tIPSDTA (include/assx.h (f11))
+    def _tipsdta_dims(self, nu, n_blocks, U, H, X, W, ws, status):
+        """(f10)'s shape checks, the degree of freedom and the workspace of (f11)."""
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, None, status, model="tIPSDTA")
+        nu = float(nu)
+        if not 0.0 < nu < float("inf"):
+            raise ValueError("tIPSDTA: nu must be finite and > 0, got %r" % (nu,))
+        need = self._L.assx_tipsdta_workspace_bytes(M, F, T, K, nb, self.prec.code, nu)
+        if ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
+            raise ValueError("tIPSDTA: workspace of %d bytes, %d needed" % (ws.numel(), need))
+        return M, F, T, K, nb, nu
+
+    def tipsdta_workspace(self, M, F, T, K, n_blocks, nu=1.0):
+        n = self._L.assx_tipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code, float(nu))
+        if n == 0:
+            raise ValueError("tIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins, "
+                             "blocks of at most 8 bins and a finite nu > 0; got dtype=%s, n_channels=%d, n_bins=%d, "
+                             "n_frames=%d, n_basis=%d, n_blocks=%d, nu=%r" % (self.prec.name, M, F, T, K, n_blocks, nu))
+        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+
+    def tipsdta_update_basis(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, status=None):
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_tipsdta_update_basis(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu, ptr(status),
+                                                      ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_tipsdta_update_basis")
+
+    def tipsdta_update_activation(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, status=None):
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_tipsdta_update_activation(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu,
+                                                           ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_tipsdta_update_activation")
+
+    def tipsdta_update_source(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, normalize=True, status=None):
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        self._check(self._L.assx_tipsdta_update_source(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu,
+                                                       int(bool(normalize)), ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64,
+                                                       self._st()), "assx_tipsdta_update_source")
+
+    def tipsdta_update_spatial(self, X, W, U, H, ws, n_blocks, nu=1.0, n_sweeps=1, eps=1e-12, status=None):
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        if int(n_sweeps) < 0:
+            raise ValueError("tIPSDTA: n_sweeps must be >= 0, got %d" % int(n_sweeps))
+        self._check(self._L.assx_tipsdta_update_spatial(self.ctx, int(n_sweeps), ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
+                                                        nu, ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
+                    "assx_tipsdta_update_spatial")
+
+    def tipsdta_loss(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, loss=None, status=None):
+        """loss (1,) float64: the negative log-likelihood of the model as it stands."""
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._ipsdta_array(loss, (1,), "loss", torch.float64, "tIPSDTA")
+        self._check(self._L.assx_tipsdta_loss(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu, ptr(loss),
+                                              ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), "assx_tipsdta_loss")
+        return loss
+
+    def tipsdta_iterate(self, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, normalize=True,
+                        loss=None, status=None):
+        """n_iter x (source update, `spatial_iteration` sweeps, loss); loss: (n_iter,) float64 or None."""
+        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
+        if int(n_iter) < 0 or int(spatial_iteration) < 0:
+            raise ValueError("tIPSDTA: n_iter and spatial_iteration must be >= 0, got %d and %d"
+                             % (int(n_iter), int(spatial_iteration)))
+        if loss is not None:
+            self._ipsdta_array(loss, (int(n_iter),), "loss", torch.float64, "tIPSDTA")
+        self._check(self._L.assx_tipsdta_iterate(self.ctx, int(n_iter), int(spatial_iteration), ptr(X), ptr(W), ptr(U), ptr(H),
+                                                 float(eps), nu, int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), M, F,
+                                                 T, K, nb, _lib.F64, self._st()), "assx_tipsdta_iterate")
 
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""

@@ -522,6 +522,45 @@ int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const 
                         int normalize, double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M, int F, int T,
                         int K, int n_blocks, int dtype, void* stream);
 
+/* ---- (f11) tIPSDTA, the Student-t block-diagonal IPSDTA (src/bss/ipsdta.py:1083-1762) --------------------------------------
+ * State, packing, envelope, psd() and `status` as in (f10); `nu` > 0 and finite is the degree of freedom (ASSX_E_ARG
+ * otherwise).  assx_ipsdta_normalize and assx_ipsdta_to_psd serve this model as they are.  Every update is weighted per
+ * (source, frame) by pi[n,t] = (nu + 2 F) / (nu + 2 sum_b q[n,b,t]), q[n,b,t] = y_b^H Ri_b y_b, the blocks added in index
+ * order.  `ws` (assx_tipsdta_workspace_bytes; 0 outside the envelope or for a bad nu, no GPU needed) is scratch:
+ * 16 (2 N P T + 2 N K P) + 8 (2 N n_blocks T + N T) bytes.
+ *   assx_tipsdta_update_basis       ipsdta.py:1268-1395: (f10)'s with S_k = sum_t H pi Ri (y y^H + eps I) Ri.
+ *   assx_tipsdta_update_activation  ipsdta.py:1397-1471: (f10)'s with num multiplied by pi before its floor at 0.
+ *   assx_tipsdta_update_source      basis, activation, assx_ipsdta_normalize if `normalize`.
+ *   assx_tipsdta_update_spatial     ipsdta.py:1473-1654, n_sweeps times: Ri once, then per sweep the steps (source n; the low
+ *                                   blocks at position 0..nn-1, then the high blocks at position 0..nn).  A step: pi_n from
+ *                                   the current q of ALL blocks; Q = psd(mean_t pi (Ri)_ii (x x^H + eps |x|^2 I)) and gamma =
+ *                                   mean_t pi sum_{j != i} (Ri)_ji x conj(y_j) per block of the group; (f10)'s solves and row
+ *                                   update; q of the stepped blocks from the new row.  Two launches per step, stream order
+ *                                   is the only coupling between blocks; every sweep starts with a pass that forms q of
+ *                                   all blocks, so n sweeps in one call equal n calls of one sweep bit for bit.
+ *   assx_tipsdta_loss               ipsdta.py:1694-1762: loss[0] = sum log max(lambda(R), eps) + (nu + 2 F)/2 sum_{n,t}
+ *                                   log(1 + (2/nu) sum_b q) - 2 T sum_f log|det W_f|.
+ *   assx_tipsdta_iterate            n_iter x (update_source, update_spatial, loss into loss[i] if loss != NULL), enqueued
+ *                                   without a synchronisation, bit for bit the single calls. */
+size_t assx_tipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype, double nu);
+int assx_tipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* U, const void* H, double eps, double nu,
+                              int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream);
+int assx_tipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps, double nu,
+                                   int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                   void* stream);
+int assx_tipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void* U, void* H, double eps, double nu,
+                               int normalize, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                               void* stream);
+int assx_tipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
+                                double nu, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                                void* stream);
+int assx_tipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U, const void* H, double eps, double nu,
+                      double* loss /* (1,) */, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
+                      void* stream);
+int assx_tipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
+                         double nu, int normalize, double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M,
+                         int F, int T, int K, int n_blocks, int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
