@@ -32,7 +32,9 @@
 //
 // tIPSDTA, the Student-t model of the same paper series (src/bss/ipsdta.py:1083-1762), shares the model, contraction, basis,
 // activation and normalisation kernels (the template flag TD switches its weights in; the Gauss instantiations are
-// unchanged) and adds ip_pi_kernel, ip_tstep_kernel and ip_tloss_kernel, described where they are defined.
+// unchanged) and adds ip_pi_kernel, ip_tq_kernel, ip_tstep_kernel and ip_tloss_kernel, described where they are defined.
+// The host drivers are templates on the same flag and read one workspace layout (ip_layout: a field the model does not use
+// has size 0); only the spatial updates, two different algorithms, are two functions.
 #include "assx_common.hpp"
 #include "assx_herm_linalg.hpp"
 
@@ -82,19 +84,23 @@ inline bool ip_geo(int M, int F, int T, int K, int n_blocks, IpGeo& g) {
 }
 
 struct IpLayout {
-  size_t ri, zz, part, q, lossp, total;
+  size_t ri, zz, part, q, qb, lossp, pi, total;
 };
 
-// ri, zz: (N,P,T) complex; part: S and T (N,2,K,P) complex; q: (N,F,M,M) complex; lossp: (N,n_blocks,T) double
-IpLayout ip_layout(const IpGeo& g) {
-  const size_t c = sizeof(cx), N = g.M;
+// ri, zz: (N,P,T) complex; part: S and T (N,2,K,P) complex; lossp: (N,n_blocks,T) double.  The Gauss model adds q
+// (N,F,M,M) complex, the Student-t model (td) qb (N,n_blocks,T) and pi (N,T) double.  A field the model does not use has
+// size 0
+IpLayout ip_layout(const IpGeo& g, bool td) {
+  const size_t c = sizeof(cx), N = g.M, terms = N * g.nblk * g.T * sizeof(double);
   IpLayout L;
   L.ri = 0;
   L.zz = L.ri + N * g.P * g.T * c;
   L.part = L.zz + N * g.P * g.T * c;
   L.q = L.part + N * 2 * g.K * g.P * c;
-  L.lossp = L.q + N * g.F * g.M * g.M * c;
-  L.total = L.lossp + N * g.nblk * g.T * sizeof(double);
+  L.qb = L.q + (td ? 0 : N * g.F * g.M * g.M * c);
+  L.lossp = L.qb + (td ? terms : 0);
+  L.pi = L.lossp + terms;
+  L.total = L.pi + (td ? N * g.T * sizeof(double) : 0);
   return L;
 }
 
@@ -688,144 +694,6 @@ __global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, 
   if (threadIdx.x == 0) loss[0] = v - 2.0 * (double)g.T * ldw;
 }
 
-#define IP_NB_SWITCH(nb, ...)                                   \
-  switch (nb) {                                                 \
-    case 1: { constexpr int NB = 1; __VA_ARGS__; } break;       \
-    case 2: { constexpr int NB = 2; __VA_ARGS__; } break;       \
-    case 3: { constexpr int NB = 3; __VA_ARGS__; } break;       \
-    case 4: { constexpr int NB = 4; __VA_ARGS__; } break;       \
-    case 5: { constexpr int NB = 5; __VA_ARGS__; } break;       \
-    case 6: { constexpr int NB = 6; __VA_ARGS__; } break;       \
-    case 7: { constexpr int NB = 7; __VA_ARGS__; } break;       \
-    case 8: { constexpr int NB = 8; __VA_ARGS__; } break;       \
-    default: break;                                             \
-  }
-
-struct IpArgs {
-  const cx* X;
-  cx* W;
-  cx* U;
-  double* H;
-  double eps;
-  int32_t* status;
-  char* ws;
-  IpGeo g;
-  hipStream_t st;
-  double nu;  // the Student-t entry points only
-};
-
-inline unsigned ip_grid(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
-
-// the model kernel over the low blocks, then over the high ones
-template <int MODE, bool TD>
-int ip_model_at(assx_ctx* ctx, const IpArgs& a, cx* ri, cx* zz, double* lossp, double* qb) {
-  const IpGeo& g = a.g;
-  for (int part = 0; part < 2; ++part) {
-    const int b0 = part ? g.nlow : 0, nbk = part ? g.nblk - g.nlow : g.nlow, nb = g.nn + part;
-    if (nbk == 0) continue;
-    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_model_kernel<NB, MODE, TD>), dim3(ip_grid((size_t)g.M * nbk * g.T)), dim3(BLK),
-                                        0, a.st, a.X, (const cx*)a.W, (const cx*)a.U, (const double*)a.H, ri, zz, lossp,
-                                        a.status, a.eps, g, b0, nbk, qb));
-    ASSX_LAUNCH_CHECK(ctx, "ip_model_kernel");
-  }
-  return 0;
-}
-
-template <int MODE>
-int ip_model(assx_ctx* ctx, const IpArgs& a) {
-  const IpLayout L = ip_layout(a.g);
-  return ip_model_at<MODE, false>(ctx, a, (cx*)(a.ws + L.ri), (cx*)(a.ws + L.zz), (double*)(a.ws + L.lossp), nullptr);
-}
-
-int ip_update_basis(assx_ctx* ctx, const IpArgs& a) {
-  const IpGeo& g = a.g;
-  const IpLayout L = ip_layout(g);
-  cx *ri = (cx*)(a.ws + L.ri), *zz = (cx*)(a.ws + L.zz), *part = (cx*)(a.ws + L.part);
-  int rc = ip_model<MODE_BASIS>(ctx, a);
-  if (rc) return rc;
-  const size_t waves = (size_t)g.M * g.P;
-  hipLaunchKernelGGL((ip_contract_kernel<false>), dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st, (const double*)a.H,
-                     (const cx*)ri, (const cx*)zz, part, g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_contract_kernel");
-  for (int p = 0; p < 2; ++p) {
-    const int b0 = p ? g.nlow : 0, nbk = p ? g.nblk - g.nlow : g.nlow, nb = g.nn + p;
-    if (nbk == 0) continue;
-    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_basis_kernel<NB>), dim3(ip_grid((size_t)g.M * g.K * nbk)), dim3(BLK), 0, a.st,
-                                        a.U, (const cx*)part, a.status, a.eps, g, b0, nbk));
-    ASSX_LAUNCH_CHECK(ctx, "ip_basis_kernel");
-  }
-  return 0;
-}
-
-int ip_update_activation(assx_ctx* ctx, const IpArgs& a) {
-  const IpGeo& g = a.g;
-  const IpLayout L = ip_layout(g);
-  int rc = ip_model<MODE_ACT>(ctx, a);
-  if (rc) return rc;
-  hipLaunchKernelGGL((ip_act_kernel<false>), dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
-                     (const cx*)(a.ws + L.ri), (const cx*)(a.ws + L.zz), a.eps, g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_act_kernel");
-  return 0;
-}
-
-int ip_normalize(assx_ctx* ctx, const IpArgs& a) {
-  hipLaunchKernelGGL(ip_norm_kernel, dim3((unsigned)(a.g.M * a.g.K)), dim3(BLK), 0, a.st, a.U, a.H, a.g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_norm_kernel");
-  return 0;
-}
-
-int ip_update_source(assx_ctx* ctx, const IpArgs& a, int normalize) {
-  int rc = ip_update_basis(ctx, a);
-  if (rc) return rc;
-  rc = ip_update_activation(ctx, a);
-  if (rc) return rc;
-  return normalize ? ip_normalize(ctx, a) : 0;
-}
-
-int ip_update_spatial(assx_ctx* ctx, const IpArgs& a, int n_sweeps) {
-  if (n_sweeps <= 0) return 0;
-  const IpGeo& g = a.g;
-  const IpLayout L = ip_layout(g);
-  cx *ri = (cx*)(a.ws + L.ri), *q = (cx*)(a.ws + L.q);
-  int rc = ip_model<MODE_SPATIAL>(ctx, a);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ip_q_kernel, dim3((unsigned)(g.M * g.F)), dim3(WAVE), 0, a.st, a.X, (const cx*)ri, q, a.eps, g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_q_kernel");
-  const size_t nq = (size_t)g.M * g.F;
-  IP_NB_SWITCH(g.M, hipLaunchKernelGGL((ip_topsd_kernel<NB>), dim3(ip_grid(nq)), dim3(BLK), 0, a.st, q, nq, a.eps));
-  ASSX_LAUNCH_CHECK(ctx, "ip_topsd_kernel");
-  for (int s = 0; s < n_sweeps; ++s) {
-    hipLaunchKernelGGL(ip_sweep_kernel, dim3((unsigned)g.nblk), dim3(BLK), 0, a.st, a.X, a.W, (const cx*)ri, (const cx*)q,
-                       a.status, a.eps, g);
-    ASSX_LAUNCH_CHECK(ctx, "ip_sweep_kernel");
-  }
-  return 0;
-}
-
-int ip_loss(assx_ctx* ctx, const IpArgs& a, double* loss) {
-  const IpLayout L = ip_layout(a.g);
-  int rc = ip_model<MODE_LOSS>(ctx, a);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ip_loss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)(a.ws + L.lossp), loss,
-                     a.eps, a.g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_loss_kernel");
-  return 0;
-}
-
-int ip_args(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, double eps, int32_t* status, void* ws, int M,
-            int F, int T, int K, int n_blocks, int dtype, void* stream) {
-  ASSX_REQUIRE_CTX(ctx);
-  ASSX_REQUIRE(ctx, dtype == ASSX_F64 || dtype == ASSX_F32, ASSX_E_ARG, "bad dtype %d", dtype);
-  ASSX_REQUIRE(ctx, dtype == ASSX_F64, ASSX_E_UNSUPPORTED, "GaussIPSDTA: float64 only");
-  ASSX_REQUIRE(ctx, ip_geo(M, F, T, K, n_blocks, a.g), ASSX_E_ARG,
-               "GaussIPSDTA: M=%d F=%d T=%d K=%d n_blocks=%d outside the envelope (2 <= M <= 8, 1 <= K <= 64, 1 <= n_blocks "
-               "<= F, largest block <= 8)",
-               M, F, T, K, n_blocks);
-  a.X = (const cx*)X, a.W = (cx*)W, a.U = (cx*)U, a.H = (double*)H, a.eps = eps, a.status = status, a.ws = (char*)ws;
-  a.st = (hipStream_t)stream;
-  return 0;
-}
-
 // ---- the Student-t model (tIPSDTA, src/bss/ipsdta.py:1083-1762) --------------------------------------------------------
 // Every update is weighted per (source, frame) by pi[n,t] = (nu + 2 F) / (nu + 2 sum_b q[n,b,t]), q = y_b^H Ri_b y_b.  The
 // model pass writes q per block (TD above), ip_pi_kernel adds the blocks in index order.  The source model weights S_k and
@@ -833,24 +701,6 @@ int ip_args(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, 
 // the low blocks at position 0..nn-1, then the high blocks at position 0..nn), each step ip_pi_kernel for source n and then
 // ip_tstep_kernel over the blocks of the group; stream order between the two is the only coupling between blocks.  A sweep
 // starts with ip_tq_kernel, which forms q of all blocks from the current W.
-
-// ri, zz: (N,P,T) complex; part: (N,2,K,P) complex; qb, ld: (N,n_blocks,T) double; pi: (N,T) double
-struct IpTLayout {
-  size_t ri, zz, part, qb, ld, pi, total;
-};
-
-IpTLayout ip_tlayout(const IpGeo& g) {
-  const size_t c = sizeof(cx), N = g.M;
-  IpTLayout L;
-  L.ri = 0;
-  L.zz = L.ri + N * g.P * g.T * c;
-  L.part = L.zz + N * g.P * g.T * c;
-  L.qb = L.part + N * 2 * g.K * g.P * c;
-  L.ld = L.qb + N * g.nblk * g.T * sizeof(double);
-  L.pi = L.ld + N * g.nblk * g.T * sizeof(double);
-  L.total = L.pi + N * g.T * sizeof(double);
-  return L;
-}
 
 // one thread per (source, frame) of the sources n0 .. n0 + cnt - 1, the blocks in index order
 __global__ void __launch_bounds__(BLK) ip_pi_kernel(const double* __restrict__ qb, double* __restrict__ pi, double nu, IpGeo g,
@@ -1068,111 +918,230 @@ __global__ void __launch_bounds__(BLK) ip_tloss_kernel(const cx* __restrict__ W,
   if (threadIdx.x == 0) loss[0] = (v + 0.5 * (nu + 2.0 * (double)g.F) * u) - 2.0 * (double)g.T * ldw;
 }
 
-struct IpTPtrs {
-  cx *ri, *zz, *part;
-  double *qb, *ld, *pi;
+#define IP_NB_SWITCH(nb, ...)                                   \
+  switch (nb) {                                                 \
+    case 1: { constexpr int NB = 1; __VA_ARGS__; } break;       \
+    case 2: { constexpr int NB = 2; __VA_ARGS__; } break;       \
+    case 3: { constexpr int NB = 3; __VA_ARGS__; } break;       \
+    case 4: { constexpr int NB = 4; __VA_ARGS__; } break;       \
+    case 5: { constexpr int NB = 5; __VA_ARGS__; } break;       \
+    case 6: { constexpr int NB = 6; __VA_ARGS__; } break;       \
+    case 7: { constexpr int NB = 7; __VA_ARGS__; } break;       \
+    case 8: { constexpr int NB = 8; __VA_ARGS__; } break;       \
+    default: break;                                             \
+  }
+
+struct IpArgs {
+  const cx* X;
+  cx* W;
+  cx* U;
+  double* H;
+  double eps;
+  int32_t* status;
+  char* ws;
+  IpGeo g;
+  hipStream_t st;
+  double nu;  // the Student-t entry points only
 };
 
-inline IpTPtrs ip_tptrs(const IpArgs& a) {
-  const IpTLayout L = ip_tlayout(a.g);
-  return {(cx*)(a.ws + L.ri), (cx*)(a.ws + L.zz), (cx*)(a.ws + L.part), (double*)(a.ws + L.qb), (double*)(a.ws + L.ld),
-          (double*)(a.ws + L.pi)};
+struct IpPtrs {
+  cx *ri, *zz, *part, *q;
+  double *qb, *lossp, *pi;
+};
+
+inline IpPtrs ip_ptrs(const IpArgs& a, bool td) {
+  const IpLayout L = ip_layout(a.g, td);
+  return {(cx*)(a.ws + L.ri), (cx*)(a.ws + L.zz), (cx*)(a.ws + L.part), (cx*)(a.ws + L.q),
+          (double*)(a.ws + L.qb), (double*)(a.ws + L.lossp), (double*)(a.ws + L.pi)};
 }
 
-int ip_tpi(assx_ctx* ctx, const IpArgs& a, const IpTPtrs& p, int n0, int cnt) {
+inline unsigned ip_grid(size_t n) { return (unsigned)((n + BLK - 1) / BLK); }
+
+// f(b0, nbk, nb) for the low blocks (nbk blocks of nb bins from block b0 on), then for the high ones; a group without
+// blocks is left out, the first non-zero return ends the walk
+template <class Fn>
+int ip_for_groups(const IpGeo& g, Fn f) {
+  for (int h = 0; h < 2; ++h) {
+    const int b0 = h ? g.nlow : 0, nbk = h ? g.nblk - g.nlow : g.nlow;
+    if (nbk == 0) continue;
+    const int rc = f(b0, nbk, g.nn + h);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+template <int MODE, bool TD>
+int ip_model(assx_ctx* ctx, const IpArgs& a, const IpPtrs& p) {
+  const IpGeo& g = a.g;
+  return ip_for_groups(g, [&](int b0, int nbk, int nb) -> int {
+    IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_model_kernel<NB, MODE, TD>), dim3(ip_grid((size_t)g.M * nbk * g.T)), dim3(BLK),
+                                        0, a.st, a.X, (const cx*)a.W, (const cx*)a.U, (const double*)a.H, p.ri, p.zz, p.lossp,
+                                        a.status, a.eps, g, b0, nbk, TD ? p.qb : nullptr));
+    ASSX_LAUNCH_CHECK(ctx, "ip_model_kernel");
+    return 0;
+  });
+}
+
+// pi of the sources n0 .. n0 + cnt - 1 from the q of the workspace (the Student-t model)
+int ip_pi(assx_ctx* ctx, const IpArgs& a, const IpPtrs& p, int n0, int cnt) {
   hipLaunchKernelGGL(ip_pi_kernel, dim3(ip_grid((size_t)cnt * a.g.T)), dim3(BLK), 0, a.st, (const double*)p.qb, p.pi, a.nu,
                      a.g, n0, cnt);
   ASSX_LAUNCH_CHECK(ctx, "ip_pi_kernel");
   return 0;
 }
 
-int ip_tupdate_basis(assx_ctx* ctx, const IpArgs& a) {
+// the model pass of MODE and, for the Student-t model, pi of all sources: what every source-model update starts with
+template <int MODE, bool TD>
+int ip_model_pi(assx_ctx* ctx, const IpArgs& a, const IpPtrs& p) {
+  const int rc = ip_model<MODE, TD>(ctx, a, p);
+  if (rc || !TD) return rc;
+  return ip_pi(ctx, a, p, 0, a.g.M);
+}
+
+template <bool TD>
+int ip_update_basis(assx_ctx* ctx, const IpArgs& a) {
   const IpGeo& g = a.g;
-  const IpTPtrs p = ip_tptrs(a);
-  int rc = ip_model_at<MODE_BASIS, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
-  if (rc) return rc;
-  rc = ip_tpi(ctx, a, p, 0, g.M);
+  const IpPtrs p = ip_ptrs(a, TD);
+  const int rc = ip_model_pi<MODE_BASIS, TD>(ctx, a, p);
   if (rc) return rc;
   const size_t waves = (size_t)g.M * g.P;
-  hipLaunchKernelGGL((ip_contract_kernel<true>), dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st,
-                     (const double*)a.H, (const cx*)p.ri, (const cx*)p.zz, p.part, g, (const double*)p.pi);
+  hipLaunchKernelGGL((ip_contract_kernel<TD>), dim3((unsigned)((waves + NW - 1) / NW)), dim3(BLK), 0, a.st,
+                     (const double*)a.H, (const cx*)p.ri, (const cx*)p.zz, p.part, g, TD ? (const double*)p.pi : nullptr);
   ASSX_LAUNCH_CHECK(ctx, "ip_contract_kernel");
-  for (int h = 0; h < 2; ++h) {
-    const int b0 = h ? g.nlow : 0, nbk = h ? g.nblk - g.nlow : g.nlow, nb = g.nn + h;
-    if (nbk == 0) continue;
+  return ip_for_groups(g, [&](int b0, int nbk, int nb) -> int {
     IP_NB_SWITCH(nb, hipLaunchKernelGGL((ip_basis_kernel<NB>), dim3(ip_grid((size_t)g.M * g.K * nbk)), dim3(BLK), 0, a.st,
                                         a.U, (const cx*)p.part, a.status, a.eps, g, b0, nbk));
     ASSX_LAUNCH_CHECK(ctx, "ip_basis_kernel");
-  }
-  return 0;
+    return 0;
+  });
 }
 
-int ip_tupdate_activation(assx_ctx* ctx, const IpArgs& a) {
+template <bool TD>
+int ip_update_activation(assx_ctx* ctx, const IpArgs& a) {
   const IpGeo& g = a.g;
-  const IpTPtrs p = ip_tptrs(a);
-  int rc = ip_model_at<MODE_ACT, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  const IpPtrs p = ip_ptrs(a, TD);
+  const int rc = ip_model_pi<MODE_ACT, TD>(ctx, a, p);
   if (rc) return rc;
-  rc = ip_tpi(ctx, a, p, 0, g.M);
-  if (rc) return rc;
-  hipLaunchKernelGGL((ip_act_kernel<true>), dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
-                     (const cx*)p.ri, (const cx*)p.zz, a.eps, g, (const double*)p.pi);
+  hipLaunchKernelGGL((ip_act_kernel<TD>), dim3(ip_grid((size_t)g.M * g.K * g.T)), dim3(BLK), 0, a.st, (const cx*)a.U, a.H,
+                     (const cx*)p.ri, (const cx*)p.zz, a.eps, g, TD ? (const double*)p.pi : nullptr);
   ASSX_LAUNCH_CHECK(ctx, "ip_act_kernel");
   return 0;
 }
 
-int ip_tupdate_source(assx_ctx* ctx, const IpArgs& a, int normalize) {
-  int rc = ip_tupdate_basis(ctx, a);
+int ip_normalize(assx_ctx* ctx, const IpArgs& a) {
+  hipLaunchKernelGGL(ip_norm_kernel, dim3((unsigned)(a.g.M * a.g.K)), dim3(BLK), 0, a.st, a.U, a.H, a.g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_norm_kernel");
+  return 0;
+}
+
+template <bool TD>
+int ip_update_source(assx_ctx* ctx, const IpArgs& a, int normalize) {
+  int rc = ip_update_basis<TD>(ctx, a);
   if (rc) return rc;
-  rc = ip_tupdate_activation(ctx, a);
+  rc = ip_update_activation<TD>(ctx, a);
   if (rc) return rc;
   return normalize ? ip_normalize(ctx, a) : 0;
 }
 
-// 1 or 2 model launches, then per sweep the q pass and N (nn + (nn + 1 if there are high blocks)) steps of 2 launches
+// the Gauss model: Q once, then the sweeps
+int ip_update_spatial(assx_ctx* ctx, const IpArgs& a, int n_sweeps) {
+  if (n_sweeps <= 0) return 0;
+  const IpGeo& g = a.g;
+  const IpPtrs p = ip_ptrs(a, false);
+  int rc = ip_model<MODE_SPATIAL, false>(ctx, a, p);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ip_q_kernel, dim3((unsigned)(g.M * g.F)), dim3(WAVE), 0, a.st, a.X, (const cx*)p.ri, p.q, a.eps, g);
+  ASSX_LAUNCH_CHECK(ctx, "ip_q_kernel");
+  const size_t nq = (size_t)g.M * g.F;
+  IP_NB_SWITCH(g.M, hipLaunchKernelGGL((ip_topsd_kernel<NB>), dim3(ip_grid(nq)), dim3(BLK), 0, a.st, p.q, nq, a.eps));
+  ASSX_LAUNCH_CHECK(ctx, "ip_topsd_kernel");
+  for (int s = 0; s < n_sweeps; ++s) {
+    hipLaunchKernelGGL(ip_sweep_kernel, dim3((unsigned)g.nblk), dim3(BLK), 0, a.st, a.X, a.W, (const cx*)p.ri, (const cx*)p.q,
+                       a.status, a.eps, g);
+    ASSX_LAUNCH_CHECK(ctx, "ip_sweep_kernel");
+  }
+  return 0;
+}
+
+// the Student-t model: 1 or 2 model launches, then per sweep the q pass and N (nn + (nn + 1 if there are high blocks))
+// steps of 2 launches
 int ip_tupdate_spatial(assx_ctx* ctx, const IpArgs& a, int n_sweeps) {
   if (n_sweeps <= 0) return 0;
   const IpGeo& g = a.g;
-  const IpTPtrs p = ip_tptrs(a);
-  int rc = ip_model_at<MODE_SPATIAL, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+  const IpPtrs p = ip_ptrs(a, true);
+  int rc = ip_model<MODE_SPATIAL, true>(ctx, a, p);
   if (rc) return rc;
   for (int s = 0; s < n_sweeps; ++s) {
     hipLaunchKernelGGL(ip_tq_kernel, dim3(ip_grid((size_t)g.M * g.nblk * g.T)), dim3(BLK), 0, a.st, a.X, (const cx*)a.W,
                        (const cx*)p.ri, p.qb, g);
     ASSX_LAUNCH_CHECK(ctx, "ip_tq_kernel");
-    for (int n = 0; n < g.M; ++n)
-      for (int h = 0; h < 2; ++h) {
-        const int b0 = h ? g.nlow : 0, nbk = h ? g.nblk - g.nlow : g.nlow, nb = g.nn + h;
-        if (nbk == 0) continue;
+    for (int n = 0; n < g.M; ++n) {
+      rc = ip_for_groups(g, [&](int b0, int nbk, int nb) -> int {
         for (int i = 0; i < nb; ++i) {
-          rc = ip_tpi(ctx, a, p, n, 1);
-          if (rc) return rc;
+          const int rp = ip_pi(ctx, a, p, n, 1);
+          if (rp) return rp;
           IP_NB_SWITCH(g.M, hipLaunchKernelGGL((ip_tstep_kernel<NB>), dim3((unsigned)nbk), dim3(BLK), 0, a.st, a.X, a.W,
                                                (const cx*)p.ri, (const double*)p.pi, p.qb, a.status, a.eps, g, n, b0, i));
           ASSX_LAUNCH_CHECK(ctx, "ip_tstep_kernel");
         }
-      }
+        return 0;
+      });
+      if (rc) return rc;
+    }
   }
   return 0;
 }
 
-int ip_tloss(assx_ctx* ctx, const IpArgs& a, double* loss) {
-  const IpTPtrs p = ip_tptrs(a);
-  int rc = ip_model_at<MODE_LOSS, true>(ctx, a, p.ri, p.zz, p.ld, p.qb);
+template <bool TD>
+int ip_loss(assx_ctx* ctx, const IpArgs& a, double* loss) {
+  const IpPtrs p = ip_ptrs(a, TD);
+  const int rc = ip_model<MODE_LOSS, TD>(ctx, a, p);
   if (rc) return rc;
-  hipLaunchKernelGGL(ip_tloss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)p.ld, (const double*)p.qb,
-                     loss, a.nu, a.eps, a.g);
-  ASSX_LAUNCH_CHECK(ctx, "ip_tloss_kernel");
+  if (TD) {
+    hipLaunchKernelGGL(ip_tloss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)p.lossp,
+                       (const double*)p.qb, loss, a.nu, a.eps, a.g);
+    ASSX_LAUNCH_CHECK(ctx, "ip_tloss_kernel");
+  } else {
+    hipLaunchKernelGGL(ip_loss_kernel, dim3(1), dim3(BLK), 0, a.st, (const cx*)a.W, (const double*)p.lossp, loss, a.eps, a.g);
+    ASSX_LAUNCH_CHECK(ctx, "ip_loss_kernel");
+  }
+  return 0;
+}
+
+// n_iter x (source update, `spatial_iteration` sweeps, the loss if asked for)
+template <bool TD>
+int ip_iterate(assx_ctx* ctx, const IpArgs& a, int n_iter, int spatial_iteration, int normalize, double* loss) {
+  for (int it = 0; it < n_iter; ++it) {
+    int rc = ip_update_source<TD>(ctx, a, normalize);
+    if (rc) return rc;
+    rc = TD ? ip_tupdate_spatial(ctx, a, spatial_iteration) : ip_update_spatial(ctx, a, spatial_iteration);
+    if (rc) return rc;
+    if (loss) {
+      rc = ip_loss<TD>(ctx, a, loss + it);
+      if (rc) return rc;
+    }
+  }
   return 0;
 }
 
 inline bool ip_nu_ok(double nu) { return nu > 0.0 && nu <= 1.7976931348623157e308; }
 
-int ip_targs(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, double eps, double nu, int32_t* status,
-             void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
-  int rc = ip_args(ctx, a, X, W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
-  if (rc) return rc;
-  ASSX_REQUIRE(ctx, ip_nu_ok(nu), ASSX_E_ARG, "tIPSDTA: nu = %g (finite and > 0)", nu);
-  a.nu = nu;
+// nu: the degree of freedom of the Student-t entry points, nullptr for the Gauss ones
+int ip_args(assx_ctx* ctx, IpArgs& a, const void* X, void* W, void* U, void* H, double eps, int32_t* status, void* ws, int M,
+            int F, int T, int K, int n_blocks, int dtype, void* stream, const double* nu = nullptr) {
+  ASSX_REQUIRE_CTX(ctx);
+  ASSX_REQUIRE(ctx, dtype == ASSX_F64 || dtype == ASSX_F32, ASSX_E_ARG, "bad dtype %d", dtype);
+  ASSX_REQUIRE(ctx, dtype == ASSX_F64, ASSX_E_UNSUPPORTED, "GaussIPSDTA: float64 only");
+  ASSX_REQUIRE(ctx, ip_geo(M, F, T, K, n_blocks, a.g), ASSX_E_ARG,
+               "GaussIPSDTA: M=%d F=%d T=%d K=%d n_blocks=%d outside the envelope (2 <= M <= 8, 1 <= K <= 64, 1 <= n_blocks "
+               "<= F, largest block <= 8)",
+               M, F, T, K, n_blocks);
+  a.X = (const cx*)X, a.W = (cx*)W, a.U = (cx*)U, a.H = (double*)H, a.eps = eps, a.status = status, a.ws = (char*)ws;
+  a.st = (hipStream_t)stream;
+  if (nu) {
+    ASSX_REQUIRE(ctx, ip_nu_ok(*nu), ASSX_E_ARG, "tIPSDTA: nu = %g (finite and > 0)", *nu);
+    a.nu = *nu;
+  }
   return 0;
 }
 
@@ -1183,7 +1152,7 @@ extern "C" {
 size_t assx_ipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype) {
   IpGeo g;
   if (dtype != ASSX_F64 || !ip_geo(M, F, T, K, n_blocks, g)) return 0;
-  return ip_layout(g).total;
+  return ip_layout(g, false).total;
 }
 
 int assx_ipsdta_to_psd(assx_ctx* ctx, void* A, int n_mat, int nb, double eps, void* stream) {
@@ -1203,7 +1172,7 @@ int assx_ipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* 
   int rc = ip_args(ctx, a, X, (void*)W, U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_basis: NULL array");
-  return ip_update_basis(ctx, a);
+  return ip_update_basis<false>(ctx, a);
 }
 
 int assx_ipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps,
@@ -1213,7 +1182,7 @@ int assx_ipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, c
   int rc = ip_args(ctx, a, X, (void*)W, (void*)U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_activation: NULL array");
-  return ip_update_activation(ctx, a);
+  return ip_update_activation<false>(ctx, a);
 }
 
 int assx_ipsdta_normalize(assx_ctx* ctx, void* U, void* H, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
@@ -1230,7 +1199,7 @@ int assx_ipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void*
   int rc = ip_args(ctx, a, X, (void*)W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_update_source: NULL array");
-  return ip_update_source(ctx, a, normalize);
+  return ip_update_source<false>(ctx, a, normalize);
 }
 
 int assx_ipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
@@ -1249,7 +1218,7 @@ int assx_ipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U,
   int rc = ip_args(ctx, a, X, (void*)W, (void*)U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && loss && ws, ASSX_E_NULL, "assx_ipsdta_loss: NULL array");
-  return ip_loss(ctx, a, loss);
+  return ip_loss<false>(ctx, a, loss);
 }
 
 int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
@@ -1261,59 +1230,49 @@ int assx_ipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const 
   ASSX_REQUIRE(ctx, n_iter >= 0 && spatial_iteration >= 0, ASSX_E_ARG, "assx_ipsdta_iterate: n_iter = %d, spatial_iteration = %d",
                n_iter, spatial_iteration);
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_ipsdta_iterate: NULL array");
-  for (int it = 0; it < n_iter; ++it) {
-    rc = ip_update_source(ctx, a, normalize);
-    if (rc) return rc;
-    rc = ip_update_spatial(ctx, a, spatial_iteration);
-    if (rc) return rc;
-    if (loss) {
-      rc = ip_loss(ctx, a, loss + it);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+  return ip_iterate<false>(ctx, a, n_iter, spatial_iteration, normalize, loss);
 }
 
 size_t assx_tipsdta_workspace_bytes(int M, int F, int T, int K, int n_blocks, int dtype, double nu) {
   IpGeo g;
   if (dtype != ASSX_F64 || !ip_nu_ok(nu) || !ip_geo(M, F, T, K, n_blocks, g)) return 0;
-  return ip_tlayout(g).total;
+  return ip_layout(g, true).total;
 }
 
 int assx_tipsdta_update_basis(assx_ctx* ctx, const void* X, const void* W, void* U, const void* H, double eps, double nu,
                               int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype, void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, (void*)W, U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, (void*)W, U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_basis: NULL array");
-  return ip_tupdate_basis(ctx, a);
+  return ip_update_basis<true>(ctx, a);
 }
 
 int assx_tipsdta_update_activation(assx_ctx* ctx, const void* X, const void* W, const void* U, void* H, double eps, double nu,
                                    int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
                                    void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, (void*)W, (void*)U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, (void*)W, (void*)U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_activation: NULL array");
-  return ip_tupdate_activation(ctx, a);
+  return ip_update_activation<true>(ctx, a);
 }
 
 int assx_tipsdta_update_source(assx_ctx* ctx, const void* X, const void* W, void* U, void* H, double eps, double nu,
                                int normalize, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
                                void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, (void*)W, U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, (void*)W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_source: NULL array");
-  return ip_tupdate_source(ctx, a, normalize);
+  return ip_update_source<true>(ctx, a, normalize);
 }
 
 int assx_tipsdta_update_spatial(assx_ctx* ctx, int n_sweeps, const void* X, void* W, const void* U, const void* H, double eps,
                                 double nu, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
                                 void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, W, (void*)U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, W, (void*)U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, n_sweeps >= 0, ASSX_E_ARG, "assx_tipsdta_update_spatial: n_sweeps = %d", n_sweeps);
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_update_spatial: NULL array");
@@ -1324,32 +1283,22 @@ int assx_tipsdta_loss(assx_ctx* ctx, const void* X, const void* W, const void* U
                       double* loss, int32_t* status, void* ws, int M, int F, int T, int K, int n_blocks, int dtype,
                       void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, (void*)W, (void*)U, (void*)H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, (void*)W, (void*)U, (void*)H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && W && U && H && loss && ws, ASSX_E_NULL, "assx_tipsdta_loss: NULL array");
-  return ip_tloss(ctx, a, loss);
+  return ip_loss<true>(ctx, a, loss);
 }
 
 int assx_tipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const void* X, void* W, void* U, void* H, double eps,
                          double nu, int normalize, double* loss, int32_t* status, void* ws, int M, int F, int T, int K,
                          int n_blocks, int dtype, void* stream) {
   IpArgs a;
-  int rc = ip_targs(ctx, a, X, W, U, H, eps, nu, status, ws, M, F, T, K, n_blocks, dtype, stream);
+  int rc = ip_args(ctx, a, X, W, U, H, eps, status, ws, M, F, T, K, n_blocks, dtype, stream, &nu);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, n_iter >= 0 && spatial_iteration >= 0, ASSX_E_ARG,
                "assx_tipsdta_iterate: n_iter = %d, spatial_iteration = %d", n_iter, spatial_iteration);
   ASSX_REQUIRE(ctx, X && W && U && H && ws, ASSX_E_NULL, "assx_tipsdta_iterate: NULL array");
-  for (int it = 0; it < n_iter; ++it) {
-    rc = ip_tupdate_source(ctx, a, normalize);
-    if (rc) return rc;
-    rc = ip_tupdate_spatial(ctx, a, spatial_iteration);
-    if (rc) return rc;
-    if (loss) {
-      rc = ip_tloss(ctx, a, loss + it);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+  return ip_iterate<true>(ctx, a, n_iter, spatial_iteration, normalize, loss);
 }
 
 }  // extern "C"

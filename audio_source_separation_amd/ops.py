@@ -820,8 +820,10 @@ class Engine:
         if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
             raise ValueError("%s: %s has shape %s, needs %s (contiguous)" % (model, name, tuple(a.shape), tuple(shape)))
 
-    def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None, model="GaussIPSDTA"):
-        """Shapes are checked here, where they are still known: the C-ABI takes pointers and sizes."""
+    def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None, nu=None):
+        """Shapes are checked here, where they are still known: the C-ABI takes pointers and sizes.  nu: None for (f10),
+        the degree of freedom for (f11), whose workspace is then the one checked."""
+        model = "GaussIPSDTA" if nu is None else "tIPSDTA"
         if U.dim() != 3 or H.dim() != 3:
             raise ValueError("%s: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
                              % (model, tuple(U.shape), tuple(H.shape)))
@@ -844,11 +846,39 @@ class Engine:
             self._ipsdta_array(X, (M, F, T), "input", torch.complex128, model)
         if W is not None:
             self._ipsdta_array(W, (F, M, M), "demix_filter", torch.complex128, model)
-        if ws is not None and (ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need):
-            raise ValueError("%s: workspace of %d bytes, %d needed" % (model, ws.numel(), need))
         if status is not None:
             self._ipsdta_array(status, (1,), "status", torch.int32, model)
+        if nu is not None:
+            nu = float(nu)
+            if not 0.0 < nu < float("inf"):
+                raise ValueError("tIPSDTA: nu must be finite and > 0, got %r" % (nu,))
+            need = self._L.assx_tipsdta_workspace_bytes(M, F, T, K, n_blocks, self.prec.code, nu)
+        if ws is not None and (ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need):
+            raise ValueError("%s: workspace of %d bytes, %d needed" % (model, ws.numel(), need))
         return M, F, T, K, n_blocks
+
+    def _ipsdta_call(self, entry, nu, X, W, U, H, ws, n_blocks, eps, status, lead=(), mid=(), counts=None, loss=None):
+        """The dims check and the call of assx_ipsdta_<entry> (nu None) or assx_tipsdta_<entry>: `lead` goes before X, nu
+        after eps, `mid` after nu.  counts: (message, values) of the arguments that must be >= 0; loss: (array, shape)."""
+        model, name = ("GaussIPSDTA", "assx_ipsdta_" + entry) if nu is None else ("tIPSDTA", "assx_tipsdta_" + entry)
+        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status, nu)
+        if counts is not None and min(counts[1]) < 0:
+            raise ValueError("%s: %s must be >= 0, got %s" % (model, counts[0], " and ".join("%d" % v for v in counts[1])))
+        if loss is not None:
+            self._ipsdta_array(loss[0], loss[1], "loss", torch.float64, model)
+        args = tuple(lead) + (ptr(X), ptr(W), ptr(U), ptr(H), float(eps)) + (() if nu is None else (float(nu),)) + tuple(mid)
+        self._check(getattr(self._L, name)(self.ctx, *args, ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), name)
+
+    def _ipsdta_loss(self, nu, X, W, U, H, ws, n_blocks, eps, loss, status):
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._ipsdta_call("loss", nu, X, W, U, H, ws, n_blocks, eps, status, mid=(ptr(loss),), loss=(loss, (1,)))
+        return loss
+
+    def _ipsdta_iterate(self, nu, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps, normalize, loss, status):
+        n_iter, sp = int(n_iter), int(spatial_iteration)
+        self._ipsdta_call("iterate", nu, X, W, U, H, ws, n_blocks, eps, status, lead=(n_iter, sp),
+                          mid=(int(bool(normalize)), ptr(loss)), counts=("n_iter and spatial_iteration", (n_iter, sp)),
+                          loss=None if loss is None else (loss, (n_iter,)))
 
     def ipsdta_workspace(self, M, F, T, K, n_blocks):
         n = self._L.assx_ipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code)
@@ -868,15 +898,10 @@ class Engine:
         return A
 
     def ipsdta_update_basis(self, X, W, U, H, ws, n_blocks, eps=1e-12, status=None):
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_ipsdta_update_basis(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(status), ptr(ws),
-                                                     M, F, T, K, nb, _lib.F64, self._st()), "assx_ipsdta_update_basis")
+        self._ipsdta_call("update_basis", None, X, W, U, H, ws, n_blocks, eps, status)
 
     def ipsdta_update_activation(self, X, W, U, H, ws, n_blocks, eps=1e-12, status=None):
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_ipsdta_update_activation(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(status),
-                                                          ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
-                    "assx_ipsdta_update_activation")
+        self._ipsdta_call("update_activation", None, X, W, U, H, ws, n_blocks, eps, status)
 
     def ipsdta_normalize(self, U, H, n_bins, n_blocks):
         if U.dim() != 3 or H.dim() != 3:
@@ -892,53 +917,22 @@ class Engine:
                     "assx_ipsdta_normalize")
 
     def ipsdta_update_source(self, X, W, U, H, ws, n_blocks, eps=1e-12, normalize=True, status=None):
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_ipsdta_update_source(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
-                                                      int(bool(normalize)), ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64,
-                                                      self._st()), "assx_ipsdta_update_source")
+        self._ipsdta_call("update_source", None, X, W, U, H, ws, n_blocks, eps, status, mid=(int(bool(normalize)),))
 
     def ipsdta_update_spatial(self, X, W, U, H, ws, n_blocks, n_sweeps=1, eps=1e-12, status=None):
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        if int(n_sweeps) < 0:
-            raise ValueError("GaussIPSDTA: n_sweeps must be >= 0, got %d" % int(n_sweeps))
-        self._check(self._L.assx_ipsdta_update_spatial(self.ctx, int(n_sweeps), ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
-                                                       ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
-                    "assx_ipsdta_update_spatial")
+        self._ipsdta_call("update_spatial", None, X, W, U, H, ws, n_blocks, eps, status, lead=(int(n_sweeps),),
+                          counts=("n_sweeps", (int(n_sweeps),)))
 
     def ipsdta_loss(self, X, W, U, H, ws, n_blocks, eps=1e-12, loss=None, status=None):
         """loss (1,) float64: the negative log-likelihood of the model as it stands."""
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
-        self._ipsdta_array(loss, (1,), "loss", torch.float64)
-        self._check(self._L.assx_ipsdta_loss(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), ptr(loss), ptr(status),
-                                             ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), "assx_ipsdta_loss")
-        return loss
+        return self._ipsdta_loss(None, X, W, U, H, ws, n_blocks, eps, loss, status)
 
     def ipsdta_iterate(self, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps=1e-12, normalize=True, loss=None,
                        status=None):
         """n_iter x (source update, `spatial_iteration` sweeps, loss); loss: (n_iter,) float64 or None."""
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status)
-        if int(n_iter) < 0 or int(spatial_iteration) < 0:
-            raise ValueError("GaussIPSDTA: n_iter and spatial_iteration must be >= 0, got %d and %d"
-                             % (int(n_iter), int(spatial_iteration)))
-        if loss is not None:
-            self._ipsdta_array(loss, (int(n_iter),), "loss", torch.float64)
-        self._check(self._L.assx_ipsdta_iterate(self.ctx, int(n_iter), int(spatial_iteration), ptr(X), ptr(W), ptr(U), ptr(H),
-                                                float(eps), int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), M, F, T, K,
-                                                nb, _lib.F64, self._st()), "assx_ipsdta_iterate")
+        self._ipsdta_iterate(None, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps, normalize, loss, status)
 
     # ------------------------------------------------------------------ tIPSDTA (include/assx.h (f11))
-    def _tipsdta_dims(self, nu, n_blocks, U, H, X, W, ws, status):
-        """(f10)'s shape checks, the degree of freedom and the workspace of (f11)."""
-        M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, None, status, model="tIPSDTA")
-        nu = float(nu)
-        if not 0.0 < nu < float("inf"):
-            raise ValueError("tIPSDTA: nu must be finite and > 0, got %r" % (nu,))
-        need = self._L.assx_tipsdta_workspace_bytes(M, F, T, K, nb, self.prec.code, nu)
-        if ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
-            raise ValueError("tIPSDTA: workspace of %d bytes, %d needed" % (ws.numel(), need))
-        return M, F, T, K, nb, nu
-
     def tipsdta_workspace(self, M, F, T, K, n_blocks, nu=1.0):
         n = self._L.assx_tipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code, float(nu))
         if n == 0:
@@ -948,52 +942,26 @@ class Engine:
         return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
 
     def tipsdta_update_basis(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, status=None):
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_tipsdta_update_basis(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu, ptr(status),
-                                                      ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
-                    "assx_tipsdta_update_basis")
+        self._ipsdta_call("update_basis", nu, X, W, U, H, ws, n_blocks, eps, status)
 
     def tipsdta_update_activation(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, status=None):
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_tipsdta_update_activation(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu,
-                                                           ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
-                    "assx_tipsdta_update_activation")
+        self._ipsdta_call("update_activation", nu, X, W, U, H, ws, n_blocks, eps, status)
 
     def tipsdta_update_source(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, normalize=True, status=None):
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        self._check(self._L.assx_tipsdta_update_source(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu,
-                                                       int(bool(normalize)), ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64,
-                                                       self._st()), "assx_tipsdta_update_source")
+        self._ipsdta_call("update_source", nu, X, W, U, H, ws, n_blocks, eps, status, mid=(int(bool(normalize)),))
 
     def tipsdta_update_spatial(self, X, W, U, H, ws, n_blocks, nu=1.0, n_sweeps=1, eps=1e-12, status=None):
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        if int(n_sweeps) < 0:
-            raise ValueError("tIPSDTA: n_sweeps must be >= 0, got %d" % int(n_sweeps))
-        self._check(self._L.assx_tipsdta_update_spatial(self.ctx, int(n_sweeps), ptr(X), ptr(W), ptr(U), ptr(H), float(eps),
-                                                        nu, ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()),
-                    "assx_tipsdta_update_spatial")
+        self._ipsdta_call("update_spatial", nu, X, W, U, H, ws, n_blocks, eps, status, lead=(int(n_sweeps),),
+                          counts=("n_sweeps", (int(n_sweeps),)))
 
     def tipsdta_loss(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, loss=None, status=None):
         """loss (1,) float64: the negative log-likelihood of the model as it stands."""
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
-        self._ipsdta_array(loss, (1,), "loss", torch.float64, "tIPSDTA")
-        self._check(self._L.assx_tipsdta_loss(self.ctx, ptr(X), ptr(W), ptr(U), ptr(H), float(eps), nu, ptr(loss),
-                                              ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), "assx_tipsdta_loss")
-        return loss
+        return self._ipsdta_loss(nu, X, W, U, H, ws, n_blocks, eps, loss, status)
 
     def tipsdta_iterate(self, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, normalize=True,
                         loss=None, status=None):
         """n_iter x (source update, `spatial_iteration` sweeps, loss); loss: (n_iter,) float64 or None."""
-        M, F, T, K, nb, nu = self._tipsdta_dims(nu, n_blocks, U, H, X, W, ws, status)
-        if int(n_iter) < 0 or int(spatial_iteration) < 0:
-            raise ValueError("tIPSDTA: n_iter and spatial_iteration must be >= 0, got %d and %d"
-                             % (int(n_iter), int(spatial_iteration)))
-        if loss is not None:
-            self._ipsdta_array(loss, (int(n_iter),), "loss", torch.float64, "tIPSDTA")
-        self._check(self._L.assx_tipsdta_iterate(self.ctx, int(n_iter), int(spatial_iteration), ptr(X), ptr(W), ptr(U), ptr(H),
-                                                 float(eps), nu, int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), M, F,
-                                                 T, K, nb, _lib.F64, self._st()), "assx_tipsdta_iterate")
+        self._ipsdta_iterate(nu, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps, normalize, loss, status)
 
     def hermitian_riccati(self, A, Bm, status=None):
         """H (n,M,M) complex128: the positive-definite solution of H A H = B for each of n pairs."""

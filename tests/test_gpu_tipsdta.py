@@ -4,8 +4,8 @@ path, and nu = 1e30 against the Gauss entry points.
 
 Metrics (tests/ipsdta_np.py): W per bin max|a - b| / max|b|, U per (source, basis) max|a - b| / max|b| over all its blocks,
 H entry-wise, loss |a - b| / (|b| + N n_bins n_frames), out per source max|a - b| / max|b|; tolerances come from
-tests/golden/tipsdta/tolerances.json (tools/tipsdta_tolerance_probe.py).  Every figure is printed before it is asserted
-(pytest -s shows them)."""
+tests/golden/tipsdta/tolerances.json (tools/ipsdta_tolerance_probe.py --model t).  Every figure is printed before it is
+asserted (pytest -s shows them)."""
 import os
 import sys
 
