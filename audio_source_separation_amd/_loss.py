@@ -71,3 +71,13 @@ class LazyLossList(list):
     def __array__(self, dtype=None, copy=None):
         self._flush()
         return np.array(list.copy(self), dtype=dtype)
+
+
+def append_loss(losses, loss, batched):
+    """Append the device loss `loss` (B,) to a model's `loss`: parked in HBM while that is still the LazyLossList (no
+    host sync inside a loop), else -- the caller replaced the list -- as the NumPy value the reference appends."""
+    if isinstance(losses, LazyLossList):
+        losses.append_device(loss, batched)
+    else:
+        a = loss.detach().cpu().numpy().astype(np.float64)
+        losses.append(a if batched else np.float64(a.reshape(-1)[0]))

@@ -195,6 +195,12 @@ class DeviceState:
             self._engine = Engine(dtype=self.dtype, device=self.device)
         return self._engine
 
+    def _steps_are(self, owner, names):
+        """True while every method in `names` is still `owner`'s own.  The loop goes to the one-call `*_iterate` entry only
+        then: a subclass that overrides a step keeps the Python loop, which runs what it made of it."""
+        cls = type(self)
+        return all(getattr(cls, n) is getattr(owner, n) for n in names)
+
     def _check_status(self):
         """Turn device-side flags into the exceptions NumPy would have raised (one sync)."""
         flags = int(self._status.max().item())

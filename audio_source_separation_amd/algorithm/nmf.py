@@ -12,7 +12,7 @@ import numpy as np
 
 from .._device import to_device, to_numpy, torch
 from .._state import DeviceArray, DeviceState
-from .._loss import LazyLossList
+from .._loss import LazyLossList, append_loss
 from .. import _lib
 from ..ops import Engine
 
@@ -102,10 +102,7 @@ class NMFbase(DeviceState):
     def _record_loss(self):
         loss = self._engine.nmf_loss(self._kind_code(), self._X, self._dev("T", False), self._dev("V", False),
                                      domain=self.domain, eps=self.eps, param=self._kind_param())
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, self._batched)  # no host sync inside the loop
-        else:
-            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+        append_loss(self.loss, loss, self._batched)
 
     def update(self, iteration=100):
         if iteration > 1 and self._fast_loop_ok():
@@ -429,18 +426,13 @@ class ComplexEUCNMF(ComplexNMFbase):
 
     def _fast_loop_ok(self):
         """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_cnmf_iterate when every step is this module's."""
-        cls = type(self)
-        return all(getattr(cls, n) is getattr(ComplexEUCNMF, n) for n in ("update", "update_once", "update_beta",
-                                                                           "_record_loss")) \
+        return self._steps_are(ComplexEUCNMF, ("update", "update_once", "update_beta", "_record_loss")) \
             and isinstance(self.loss, LazyLossList)
 
     def _record_loss(self):
         T, V, Phi = self._model()
         loss = self._engine.cnmf_loss(self._X, T, V, Phi, self._ws, eps=self.eps)
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, self._batched)
-        else:
-            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+        append_loss(self.loss, loss, self._batched)
 
     def update(self, iteration=100):
         if iteration > 0 and self._fast_loop_ok():

@@ -114,9 +114,7 @@ class EUCNTF(NTFbase):
 
     def _fast_loop_ok(self):
         """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_ntf_iterate when every step is this module's."""
-        cls = type(self)
-        return all(getattr(cls, n) is getattr(EUCNTF, n) for n in ("update", "update_once", "compute_loss")) \
-            and isinstance(self.loss, LazyLossList)
+        return self._steps_are(EUCNTF, ("update", "update_once", "compute_loss")) and isinstance(self.loss, LazyLossList)
 
     def update(self, target, iteration=100):
         if not self._fast_loop_ok():

@@ -191,9 +191,7 @@ class LDPSDTF(PSDTFbase):
 
     def _fast_loop_ok(self):
         """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_psdtf_iterate when every step is this module's."""
-        cls = type(self)
-        return all(getattr(cls, n) is getattr(LDPSDTF, n) for n in self._STEPS) and self.algorithm == 'mm' \
-            and isinstance(self.loss, LazyLossList)
+        return self._steps_are(LDPSDTF, self._STEPS) and self.algorithm == 'mm' and isinstance(self.loss, LazyLossList)
 
     def update(self, iteration=100):
         if not self._fast_loop_ok():

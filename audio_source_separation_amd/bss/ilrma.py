@@ -337,7 +337,7 @@ class GaussILRMA(ILRMAbase):
         overrides one keeps the loop), no partitioning function, and a normalisation the entry point knows."""
         if self.callbacks is not None or self.partitioning:
             return None
-        if any(getattr(type(self), name) is not getattr(GaussILRMA, name) for name in self._OWN_STEPS):
+        if not self._steps_are(GaussILRMA, self._OWN_STEPS):
             return None
         if self.recordable_loss and not isinstance(self.loss, LazyLossList):
             return None

@@ -20,7 +20,7 @@ import numpy as np
 from .. import _lib
 from .._device import to_device, to_numpy, torch
 from .._state import DeviceArray, DeviceState
-from .._loss import LazyLossList
+from .._loss import LazyLossList, append_loss
 
 EPS = 1e-12
 
@@ -180,7 +180,7 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
         self._reset(**kwargs)
 
         if self.recordable_loss and len(self.loss) == 0:
-            self._append_loss(self._loss_device())
+            append_loss(self.loss, self._loss_device(), False)
 
         self._run_callbacks()
 
@@ -200,7 +200,7 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
                 self.update_once()
 
                 if self.recordable_loss:
-                    self._append_loss(self._loss_device())
+                    append_loss(self.loss, self._loss_device(), False)
 
                 self._run_callbacks()
         self._check_status()
@@ -221,15 +221,8 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
     def _fast_loop_ok(self):
         """The loop goes to the model's `iterate` entry point when every step is this module's and `loss` is still the lazy
         list."""
-        cls = type(self)
-        return all(getattr(cls, n) is getattr(_BlockDiagonalIPSDTA, n) for n in self._STEPS) \
+        return self._steps_are(_BlockDiagonalIPSDTA, self._STEPS) \
             and (not self.recordable_loss or isinstance(self.loss, LazyLossList))
-
-    def _append_loss(self, loss):
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, False)
-        else:
-            self.loss.append(np.float64(loss.item()))
 
     def _run_callbacks(self):
         if self.callbacks is not None:

@@ -248,7 +248,7 @@ class AuxIVAbase(IVAbase):
     def _fast_loop_ok(self):
         if self.callbacks is not None or self._KIND is None:
             return False
-        if any(getattr(type(self), name) is not getattr(AuxIVAbase, name) for name in self._OWN_STEPS):
+        if not self._steps_are(AuxIVAbase, self._OWN_STEPS):
             return False
         if self.recordable_loss and not isinstance(self.loss, LazyLossList):
             return False

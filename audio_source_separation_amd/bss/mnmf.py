@@ -17,7 +17,7 @@ iterative-projection sweep with the normaliser floored at eps, on the very kerne
 import numpy as np
 
 from .._device import to_device, to_numpy, torch
-from .._loss import LazyLossList
+from .._loss import LazyLossList, append_loss
 from .._state import DeviceArray, DeviceState
 from .. import _lib
 from ..algorithm.projection_back import _engine
@@ -190,11 +190,7 @@ class MultichannelNMFbase(DeviceState):
 
     # ---- loss, status, callbacks -----------------------------------------------------------------------------------
     def _record_loss(self):
-        loss = self._loss_dev()
-        if isinstance(self.loss, LazyLossList):
-            self.loss.append_device(loss, self._batched)
-        else:
-            self.loss.append(to_numpy(loss, np.float64) if self._batched else np.float64(loss.item()))
+        append_loss(self.loss, self._loss_dev(), self._batched)
 
     def compute_negative_loglikelihood(self):
         """mnmf.py:538-552 (in closed form) / 890-917.  Syncs to return a Python float (an array of B with a batch
@@ -251,7 +247,7 @@ class MultichannelNMFbase(DeviceState):
         if self.callbacks is not None:
             return False
         owner = next(c for c in type(self).__mro__ if "_OWN_STEPS" in vars(c))  # the model a subclass derives from
-        if any(getattr(type(self), name) is not getattr(owner, name) for name in owner._OWN_STEPS):
+        if not self._steps_are(owner, owner._OWN_STEPS):
             return False
         return not self.recordable_loss or isinstance(self.loss, LazyLossList)
 

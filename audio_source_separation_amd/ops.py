@@ -14,6 +14,36 @@ from ._device import Precision, Workspace, context, ptr, require_gpu, stream_ptr
 _RAW = _lib.lib
 
 
+# ---------------------------------------------------------------------- argument checks of the factorisation models
+# The C-ABI takes pointers and sizes, and its kernels write float64, int32 or the model's own type through them.  An
+# array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
+# batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
+# read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF and the
+# two IPSDTA models passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# before anything is launched.
+def check_array(model, name, a, dtype, device, shape=None, numel=None):
+    """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
+    elements, any shape."""
+    if a.dtype != dtype or a.device != device:
+        raise ValueError("%s: %s must be %s on %s, got %s on %s" % (model, name, dtype, device, a.dtype, a.device))
+    fits = tuple(a.shape) == tuple(shape) if shape is not None else a.numel() >= numel
+    if not (fits and a.is_contiguous()):
+        need = "shape %s" % (tuple(shape),) if shape is not None else "at least %d elements" % numel
+        raise ValueError("%s: %s has shape %s%s, needs %s (contiguous)"
+                         % (model, name, tuple(a.shape), "" if a.is_contiguous() else " (not contiguous)", need))
+
+
+def check_workspace(model, ws, device, need):
+    """`ws` must hold at least `need` contiguous bytes as torch.uint8 on `device`; `need` is what the library's
+    *_workspace_bytes reports, 0 for sizes outside the model's envelope."""
+    if need == 0:
+        raise ValueError("%s: workspace for sizes that the model does not support" % model)
+    if ws.dtype != torch.uint8 or ws.device != device or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("%s: workspace of %d x %s%s on %s, needs at least %d contiguous bytes of torch.uint8 on %s"
+                         % (model, ws.numel(), ws.dtype, "" if ws.is_contiguous() else " (not contiguous)", ws.device,
+                            need, device))
+
+
 class _DeviceGuardedLib:
     """libassx entry points called with the engine's device made current for the duration of the call.
 
@@ -370,51 +400,53 @@ class Engine:
                     "assx_fastmnmf_update_diagonalizer")
         return Q
 
+    # ------------------------------------------------------------------ the six factorisation model families
+    # Every array and workspace goes through check_array / check_workspace (top of this module) before its address does
+    # through ptr().  A `_X_dims` holds only what is its family's own: how the sizes are read off the arrays, the range
+    # limits, the arrays wanted as (name, array, shape, dtype), the workspace query.
+    def _arg(self, model, name, a, dtype, shape=None, numel=None):
+        """check_array on this engine's device; an optional array left None passes."""
+        if a is not None:
+            check_array(model, name, a, dtype, self.dev, shape, numel)
+
+    def _args(self, model, want):
+        dev = self.dev
+        for name, a, shape, dtype in want:
+            if a is not None:
+                check_array(model, name, a, dtype, dev, shape)
+
+    def _new_workspace(self, nbytes, supports, *got):
+        """A model's own scratch of `nbytes`; 0 is the library's word for sizes outside the model's envelope."""
+        if nbytes == 0:
+            raise ValueError(supports % got)
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
+
     # ------------------------------------------------------------------ FastMNMF (bss/mnmf.py)
     def _fastmnmf_dims(self, X, W, H, g, Q=None, ws=None):
-        """Sizes of a FastMNMF call, with every array checked against them: the kernels take pointers and sizes, so an
-        array of another shape (a separate() input longer than the fitted activation, a batched input on an unbatched
-        model, a reassigned attribute) would be read past its end.  Refused here with ValueError, before any launch."""
         if X.dim() != 4 or W.dim() != 4:
             raise ValueError("FastMNMF: expected X (B,M,F,T) and basis (B,N,F,K), got %s and %s"
                              % (tuple(X.shape), tuple(W.shape)))
         B, M, F, T = (int(d) for d in X.shape)
         N, K = int(W.shape[1]), int(W.shape[3])
-        want = {"basis": (W, (B, N, F, K)), "activation": (H, (B, N, K, T)), "spatial_covariance": (g, (B, N, F, M))}
-        if Q is not None:
-            want["diagonalizer"] = (Q, (B, F, M, M))
-        want["input"] = (X, (B, M, F, T))
-        for name, (a, shape) in want.items():
-            dt = self.prec.cplx if name in ("input", "diagonalizer") else self.prec.real
-            if a.dtype != dt or a.device != self.dev:
-                raise ValueError("FastMNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
-            if tuple(a.shape) != shape:
-                raise ValueError("FastMNMF: %s has shape %s, but the input %s needs %s"
-                                 % (name, tuple(a.shape), (B, M, F, T), shape))
+        real, cplx = self.prec.real, self.prec.cplx
+        self._args("FastMNMF", (("basis", W, (B, N, F, K), real), ("activation", H, (B, N, K, T), real),
+                                ("spatial_covariance", g, (B, N, F, M), real), ("diagonalizer", Q, (B, F, M, M), cplx),
+                                ("input", X, (B, M, F, T), cplx)))
         if ws is not None:
-            need = self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code)
-            if need == 0 or ws.numel() < need:
-                raise ValueError("FastMNMF: workspace of %d bytes, %d needed for B=%d M=%d N=%d F=%d T=%d K=%d"
-                                 % (ws.numel(), need, B, M, N, F, T, K))
+            check_workspace("FastMNMF", ws, self.dev,
+                            self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code))
         return B, M, N, F, T, K
-
-    @staticmethod
-    def _fastmnmf_need(t, n, what):
-        if t is not None and (t.numel() < n or not t.is_contiguous()):
-            raise ValueError("FastMNMF: %s needs %d contiguous elements, got %s" % (what, n, tuple(t.shape)))
 
     def fastmnmf_workspace(self, B, M, N, F, T, K):
         """A model's own scratch: it carries x~ from assx_fastmnmf_project to the NMF and SCM updates."""
-        n = self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code)
-        if n == 0:
-            raise ValueError("FastMNMF supports 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; got "
-                             "n_channels=%d, n_sources=%d, n_basis=%d" % (M, N, K))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_fastmnmf_workspace_bytes(B, M, N, F, T, K, self.prec.code),
+                                   "FastMNMF supports 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; got "
+                                   "n_channels=%d, n_sources=%d, n_basis=%d", M, N, K)
 
     def fastmnmf_project(self, X, Q, W, H, g, ws, eps=1e-12, loss=None):
         """x~ = |Q x|^2 into ws; loss (B,) float64 (or None) = the negative log-likelihood of the model as it stands."""
         B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
-        self._fastmnmf_need(loss, B, "loss")
+        self._arg("FastMNMF", "loss", loss, torch.float64, numel=B)
         self._check(self._L.assx_fastmnmf_project(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g), float(eps), ptr(loss),
                                                   ptr(ws), B, M, N, F, T, K, self.prec.code, self._st()),
                     "assx_fastmnmf_project")
@@ -432,7 +464,7 @@ class Engine:
 
     def fastmnmf_update_diagonalizer_model(self, X, Q, W, H, g, ws, eps=1e-12, threshold=1e12, status=None):
         B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
-        self._fastmnmf_need(status, B, "status")
+        self._arg("FastMNMF", "status", status, torch.int32, numel=B)
         self._check(self._L.assx_fastmnmf_update_diagonalizer_model(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g),
                                                                     float(eps), float(threshold), ptr(status), ptr(ws), B,
                                                                     M, N, F, T, K, self.prec.code, self._st()),
@@ -447,9 +479,9 @@ class Engine:
     def fastmnmf_separate(self, X, Q, W, H, g, ref=0, eps=1e-12, status=None, out=None):
         """(B,N,F,T) complex: x_hat[:, ref] of the reference's separate."""
         B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q)
-        self._fastmnmf_need(status, B, "status")
+        self._arg("FastMNMF", "status", status, torch.int32, numel=B)
         Y = out if out is not None else self.empty((B, N, F, T), complex_=True)
-        self._fastmnmf_need(Y, B * N * F * T, "out")
+        self._arg("FastMNMF", "out", Y, self.prec.cplx, numel=B * N * F * T)
         self._check(self._L.assx_fastmnmf_separate(self.ctx, ptr(X), ptr(Q), ptr(W), ptr(H), ptr(g), int(ref), float(eps),
                                                    ptr(Y), ptr(status), B, M, N, F, T, K, self.prec.code, self._st()),
                     "assx_fastmnmf_separate")
@@ -459,8 +491,8 @@ class Engine:
                          loss=None):
         """loss: (n_iter + 1, B) float64 or None."""
         B, M, N, F, T, K = self._fastmnmf_dims(X, W, H, g, Q, ws)
-        self._fastmnmf_need(loss, (int(n_iter) + 1) * B, "loss")
-        self._fastmnmf_need(status, B, "status")
+        self._arg("FastMNMF", "loss", loss, torch.float64, numel=(int(n_iter) + 1) * B)
+        self._arg("FastMNMF", "status", status, torch.int32, numel=B)
         self._check(self._L.assx_fastmnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Q), ptr(W),
                                                   ptr(H), ptr(g), float(eps), float(threshold), ptr(loss), ptr(status),
                                                   ptr(ws), B, M, N, F, T, K, self.prec.code, self._st()),
@@ -468,55 +500,41 @@ class Engine:
 
     # ------------------------------------------------------------------ MultichannelISNMF (bss/mnmf.py)
     def _mnmf_dims(self, X, Tb, V, Z, H, ws=None):
-        """Sizes of an MNMF call, with every array checked against them (the kernels take pointers and sizes: an array
-        of another shape would be read past its end).  Refused with ValueError before any launch."""
         if X.dim() != 4 or Z.dim() != 3:
             raise ValueError("MNMF: expected X (B,M,F,T) and latent (B,N,K), got %s and %s"
                              % (tuple(X.shape), tuple(Z.shape)))
         B, M, F, T = (int(d) for d in X.shape)
         N, K = int(Z.shape[1]), int(Z.shape[2])
-        want = {"input": (X, (B, M, F, T)), "basis": (Tb, (B, F, K)), "activation": (V, (B, K, T)),
-                "latent": (Z, (B, N, K)), "spatial": (H, (B, F, N, M, M))}
-        for name, (a, shape) in want.items():
-            dt = torch.complex128 if name in ("input", "spatial") else torch.float64
-            if a.dtype != dt or a.device != self.dev:
-                raise ValueError("MNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
-            if tuple(a.shape) != shape or not a.is_contiguous():
-                raise ValueError("MNMF: %s has shape %s, but the input %s needs %s (contiguous)"
-                                 % (name, tuple(a.shape), (B, M, F, T), shape))
+        self._args("MNMF", (("input", X, (B, M, F, T), torch.complex128), ("basis", Tb, (B, F, K), torch.float64),
+                            ("activation", V, (B, K, T), torch.float64), ("latent", Z, (B, N, K), torch.float64),
+                            ("spatial", H, (B, F, N, M, M), torch.complex128)))
         if ws is not None:
-            need = self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64)
-            if need == 0 or ws.numel() < need:
-                raise ValueError("MNMF: workspace of %d bytes, %d needed for B=%d M=%d N=%d F=%d T=%d K=%d"
-                                 % (ws.numel(), need, B, M, N, F, T, K))
+            check_workspace("MNMF", ws, self.dev, self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64))
         return B, M, N, F, T, K
 
     def mnmf_workspace(self, B, M, N, F, T, K):
-        n = self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64)
-        if n == 0:
-            raise ValueError("MNMF supports float64, 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; "
-                             "got n_channels=%d, n_sources=%d, n_basis=%d" % (M, N, K))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_mnmf_workspace_bytes(B, M, N, F, T, K, _lib.F64),
+                                   "MNMF supports float64, 2 <= n_channels <= 8, 1 <= n_sources <= 8, 1 <= n_basis <= 64; "
+                                   "got n_channels=%d, n_sources=%d, n_basis=%d", M, N, K)
 
-    def _mnmf_step(self, fn, what, X, Tb, V, Z, H, ws, eps, status):
+    def _mnmf_step(self, what, X, Tb, V, Z, H, ws, eps, status):
         B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
-        self._fastmnmf_need(status, B, "status")
-        self._check(fn(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), float(eps), ptr(status), ptr(ws), B, M, N, F,
-                       T, K, _lib.F64, self._st()), what)
+        self._arg("MNMF", "status", status, torch.int32, numel=B)
+        self._check(getattr(self._L, what)(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), float(eps), ptr(status),
+                                           ptr(ws), B, M, N, F, T, K, _lib.F64, self._st()), what)
 
     def mnmf_update_basis(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
-        self._mnmf_step(self._L.assx_mnmf_update_basis, "assx_mnmf_update_basis", X, Tb, V, Z, H, ws, eps, status)
+        self._mnmf_step("assx_mnmf_update_basis", X, Tb, V, Z, H, ws, eps, status)
 
     def mnmf_update_activation(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
-        self._mnmf_step(self._L.assx_mnmf_update_activation, "assx_mnmf_update_activation", X, Tb, V, Z, H, ws, eps,
-                        status)
+        self._mnmf_step("assx_mnmf_update_activation", X, Tb, V, Z, H, ws, eps, status)
 
     def mnmf_update_latent(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None):
-        self._mnmf_step(self._L.assx_mnmf_update_latent, "assx_mnmf_update_latent", X, Tb, V, Z, H, ws, eps, status)
+        self._mnmf_step("assx_mnmf_update_latent", X, Tb, V, Z, H, ws, eps, status)
 
     def mnmf_update_spatial(self, X, Tb, V, Z, H, ws, normalize=True, eps=1e-12, status=None):
         B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
-        self._fastmnmf_need(status, B, "status")
+        self._arg("MNMF", "status", status, torch.int32, numel=B)
         self._check(self._L.assx_mnmf_update_spatial(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H),
                                                      1 if normalize else 0, float(eps), ptr(status), ptr(ws), B, M, N,
                                                      F, T, K, _lib.F64, self._st()), "assx_mnmf_update_spatial")
@@ -524,9 +542,9 @@ class Engine:
     def mnmf_loss(self, X, Tb, V, Z, H, ws, eps=1e-12, status=None, loss=None):
         """loss (B,) float64: the negative log-likelihood of the model as it stands."""
         B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
-        self._fastmnmf_need(status, B, "status")
+        self._arg("MNMF", "status", status, torch.int32, numel=B)
         loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
-        self._fastmnmf_need(loss, B, "loss")
+        self._arg("MNMF", "loss", loss, torch.float64, numel=B)
         self._check(self._L.assx_mnmf_loss(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), float(eps), ptr(loss),
                                            ptr(status), ptr(ws), B, M, N, F, T, K, _lib.F64, self._st()),
                     "assx_mnmf_loss")
@@ -535,9 +553,9 @@ class Engine:
     def mnmf_separate(self, X, Tb, V, Z, H, ref=0, eps=1e-12, status=None, out=None):
         """(B,N,F,T) complex: lam_n (H_n P x)[ref]."""
         B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H)
-        self._fastmnmf_need(status, B, "status")
+        self._arg("MNMF", "status", status, torch.int32, numel=B)
         Y = out if out is not None else self.empty((B, N, F, T), dtype=torch.complex128)
-        self._fastmnmf_need(Y, B * N * F * T, "out")
+        self._arg("MNMF", "out", Y, torch.complex128, numel=B * N * F * T)
         self._check(self._L.assx_mnmf_separate(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Z), ptr(H), int(ref), float(eps),
                                                ptr(Y), ptr(status), B, M, N, F, T, K, _lib.F64, self._st()),
                     "assx_mnmf_separate")
@@ -546,16 +564,14 @@ class Engine:
     def mnmf_iterate(self, n_iter, X, Tb, V, Z, H, ws, normalize=True, eps=1e-12, status=None, loss=None):
         """loss: (n_iter + 1, B) float64 or None."""
         B, M, N, F, T, K = self._mnmf_dims(X, Tb, V, Z, H, ws)
-        self._fastmnmf_need(loss, (int(n_iter) + 1) * B, "loss")
-        self._fastmnmf_need(status, B, "status")
+        self._arg("MNMF", "loss", loss, torch.float64, numel=(int(n_iter) + 1) * B)
+        self._arg("MNMF", "status", status, torch.int32, numel=B)
         self._check(self._L.assx_mnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Tb), ptr(V),
                                               ptr(Z), ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), B, M, N, F,
                                               T, K, _lib.F64, self._st()), "assx_mnmf_iterate")
 
     # ------------------------------------------------------------------ ComplexEUCNMF (algorithm/nmf.py)
     def _cnmf_dims(self, Tb, V, Phi=None, X=None, ws=None):
-        """Sizes of a complex-NMF call, with every array checked against them (the kernels take pointers and sizes: an
-        array of another shape would be read past its end).  Refused with ValueError before any launch."""
         if self.prec.code != _lib.F64:
             raise ValueError("ComplexEUCNMF supports float64 only")
         if Tb.dim() != 3 or V.dim() != 3:
@@ -565,30 +581,17 @@ class Engine:
         T = int(V.shape[2])
         if not 1 <= K <= 64:
             raise ValueError("ComplexEUCNMF: n_basis must be in [1, 64], got %d" % K)
-        want = {"basis": (Tb, (B, F, K), torch.float64), "activation": (V, (B, K, T), torch.float64)}
-        if Phi is not None:
-            want["phase"] = (Phi, (B, F, K, T), torch.float64)
-        if X is not None:
-            want["target"] = (X, (B, F, T), torch.complex128)
-        for name, (a, shape, dt) in want.items():
-            if a.dtype != dt or a.device != self.dev:
-                raise ValueError("ComplexEUCNMF: %s must be %s on %s, got %s on %s" % (name, dt, self.dev, a.dtype, a.device))
-            if tuple(a.shape) != shape or not a.is_contiguous():
-                raise ValueError("ComplexEUCNMF: %s has shape %s, but the basis %s needs %s (contiguous)"
-                                 % (name, tuple(a.shape), (B, F, K), shape))
+        self._args("ComplexEUCNMF", (("basis", Tb, (B, F, K), torch.float64), ("activation", V, (B, K, T), torch.float64),
+                                     ("phase", Phi, (B, F, K, T), torch.float64),
+                                     ("target", X, (B, F, T), torch.complex128)))
         if ws is not None:
-            need = self._L.assx_cnmf_workspace_bytes(B, F, T, K, _lib.F64)
-            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
-                raise ValueError("ComplexEUCNMF: workspace of %d bytes, %d needed for B=%d F=%d T=%d K=%d"
-                                 % (ws.numel(), need, B, F, T, K))
+            check_workspace("ComplexEUCNMF", ws, self.dev, self._L.assx_cnmf_workspace_bytes(B, F, T, K, _lib.F64))
         return B, F, T, K
 
     def cnmf_workspace(self, B, F, T, K):
-        n = self._L.assx_cnmf_workspace_bytes(B, F, T, K, self.prec.code)
-        if n == 0:
-            raise ValueError("ComplexEUCNMF supports float64 and 1 <= n_basis <= 64; got dtype=%s, n_basis=%d"
-                             % (self.prec.name, K))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_cnmf_workspace_bytes(B, F, T, K, self.prec.code),
+                                   "ComplexEUCNMF supports float64 and 1 <= n_basis <= 64; got dtype=%s, n_basis=%d",
+                                   self.prec.name, K)
 
     def cnmf_update(self, X, Tb, V, Phi, ws, regularizer=0.1, p=1, eps=1e-12):
         B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
@@ -599,7 +602,7 @@ class Engine:
         """loss (B,) float64: sum |sum_k T V e^{i Phi} - X|^2 of the model as it stands."""
         B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
         loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
-        self._fastmnmf_need(loss, B, "loss")
+        self._arg("ComplexEUCNMF", "loss", loss, torch.float64, numel=B)
         self._check(self._L.assx_cnmf_loss(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(Phi), float(eps), ptr(loss), ptr(ws), B,
                                            F, T, K, _lib.F64, self._st()), "assx_cnmf_loss")
         return loss
@@ -608,7 +611,7 @@ class Engine:
         """(B,F,K,T): T V / max(sum_k T V, eps)."""
         B, F, T, K = self._cnmf_dims(Tb, V)
         Beta = out if out is not None else self.empty((B, F, K, T), dtype=torch.float64)
-        self._fastmnmf_need(Beta, B * F * K * T, "out")
+        self._arg("ComplexEUCNMF", "out", Beta, torch.float64, numel=B * F * K * T)
         self._check(self._L.assx_cnmf_beta(self.ctx, ptr(Tb), ptr(V), float(eps), ptr(Beta), B, F, T, K, _lib.F64,
                                            self._st()), "assx_cnmf_beta")
         return Beta
@@ -617,7 +620,7 @@ class Engine:
         """(B,F,T) complex: sum_k T V e^{i Phi}."""
         B, F, T, K = self._cnmf_dims(Tb, V, Phi)
         Y = out if out is not None else self.empty((B, F, T), dtype=torch.complex128)
-        self._fastmnmf_need(Y, B * F * T, "out")
+        self._arg("ComplexEUCNMF", "out", Y, torch.complex128, numel=B * F * T)
         self._check(self._L.assx_cnmf_reconstruct(self.ctx, ptr(Tb), ptr(V), ptr(Phi), ptr(Y), B, F, T, K, _lib.F64,
                                                   self._st()), "assx_cnmf_reconstruct")
         return Y
@@ -625,15 +628,13 @@ class Engine:
     def cnmf_iterate(self, n_iter, X, Tb, V, Phi, ws, regularizer=0.1, p=1, eps=1e-12, loss=None):
         """n_iter x update; loss: (n_iter, B) float64 or None."""
         B, F, T, K = self._cnmf_dims(Tb, V, Phi, X, ws)
-        self._fastmnmf_need(loss, int(n_iter) * B, "loss")
+        self._arg("ComplexEUCNMF", "loss", loss, torch.float64, numel=int(n_iter) * B)
         self._check(self._L.assx_cnmf_iterate(self.ctx, int(n_iter), ptr(X), ptr(Tb), ptr(V), ptr(Phi),
                                               float(regularizer), float(p), float(eps), ptr(loss), ptr(ws), B, F, T, K,
                                               _lib.F64, self._st()), "assx_cnmf_iterate")
 
     # ------------------------------------------------------------------ EUCNTF (algorithm/ntf.py)
     def _ntf_dims(self, Z, Tb, V, X=None, ws=None):
-        """Sizes of an NTF call, with every array checked against them (the kernels take pointers and sizes: an array of
-        another shape would be read past its end).  Refused with ValueError before any launch."""
         if self.prec.code != _lib.F64:
             raise ValueError("EUCNTF supports float64 only")
         if Z.dim() != 3 or Tb.dim() != 3 or V.dim() != 3:
@@ -645,30 +646,16 @@ class Engine:
             raise ValueError("EUCNTF: n_basis must be in [1, 64], got %d" % K)
         if not 1 <= N <= 32:
             raise ValueError("EUCNTF: n_channels must be in [1, 32], got %d" % N)
-        want = {"partitioning": (Z, (B, N, K)), "basis": (Tb, (B, I, K)), "activation": (V, (B, K, J))}
-        if X is not None:
-            want["target"] = (X, (B, N, I, J))
-        for name, (a, shape) in want.items():
-            self._ntf_array(a, shape, name)
+        self._args("EUCNTF", (("partitioning", Z, (B, N, K), torch.float64), ("basis", Tb, (B, I, K), torch.float64),
+                              ("activation", V, (B, K, J), torch.float64), ("target", X, (B, N, I, J), torch.float64)))
         if ws is not None:
-            need = self._L.assx_ntf_workspace_bytes(B, N, I, J, K, _lib.F64)
-            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
-                raise ValueError("EUCNTF: workspace of %d bytes, %d needed for B=%d N=%d I=%d J=%d K=%d"
-                                 % (ws.numel(), need, B, N, I, J, K))
+            check_workspace("EUCNTF", ws, self.dev, self._L.assx_ntf_workspace_bytes(B, N, I, J, K, _lib.F64))
         return B, N, I, J, K
 
-    def _ntf_array(self, a, shape, name):
-        if a.dtype != torch.float64 or a.device != self.dev:
-            raise ValueError("EUCNTF: %s must be torch.float64 on %s, got %s on %s" % (name, self.dev, a.dtype, a.device))
-        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
-            raise ValueError("EUCNTF: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
-
     def ntf_workspace(self, B, N, I, J, K):
-        n = self._L.assx_ntf_workspace_bytes(B, N, I, J, K, self.prec.code)
-        if n == 0:
-            raise ValueError("EUCNTF supports float64, 1 <= n_basis <= 64 and 1 <= n_channels <= 32; got dtype=%s, "
-                             "n_basis=%d, n_channels=%d" % (self.prec.name, K, N))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_ntf_workspace_bytes(B, N, I, J, K, self.prec.code),
+                                   "EUCNTF supports float64, 1 <= n_basis <= 64 and 1 <= n_channels <= 32; got dtype=%s, "
+                                   "n_basis=%d, n_channels=%d", self.prec.name, K, N)
 
     def ntf_update(self, X, Z, Tb, V, ws, eps=1e-12):
         """One update_once of (Z, Tb, V), in place."""
@@ -680,7 +667,7 @@ class Engine:
         """loss (B,) float64: sum (X - sum_k Z T V)^2 of the model as it stands."""
         B, N, I, J, K = self._ntf_dims(Z, Tb, V, X, ws)
         loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
-        self._ntf_array(loss, (B,), "loss")
+        self._arg("EUCNTF", "loss", loss, torch.float64, (B,))
         self._check(self._L.assx_ntf_loss(self.ctx, ptr(X), ptr(Z), ptr(Tb), ptr(V), ptr(loss), ptr(ws), B, N, I, J, K,
                                           _lib.F64, self._st()), "assx_ntf_loss")
         return loss
@@ -689,7 +676,7 @@ class Engine:
         """(B,N,I,J): sum_k Z T V."""
         B, N, I, J, K = self._ntf_dims(Z, Tb, V)
         Xh = out if out is not None else self.empty((B, N, I, J), dtype=torch.float64)
-        self._ntf_array(Xh, (B, N, I, J), "out")
+        self._arg("EUCNTF", "out", Xh, torch.float64, (B, N, I, J))
         self._check(self._L.assx_ntf_reconstruct(self.ctx, ptr(Z), ptr(Tb), ptr(V), ptr(Xh), B, N, I, J, K, _lib.F64,
                                                  self._st()), "assx_ntf_reconstruct")
         return Xh
@@ -699,15 +686,12 @@ class Engine:
         B, N, I, J, K = self._ntf_dims(Z, Tb, V, X, ws)
         if int(n_iter) < 0:
             raise ValueError("EUCNTF: n_iter must be >= 0, got %d" % int(n_iter))
-        if loss is not None:
-            self._ntf_array(loss, (int(n_iter), B), "loss")
+        self._arg("EUCNTF", "loss", loss, torch.float64, (int(n_iter), B))
         self._check(self._L.assx_ntf_iterate(self.ctx, int(n_iter), ptr(X), ptr(Z), ptr(Tb), ptr(V), float(eps),
                                              ptr(loss), ptr(ws), B, N, I, J, K, _lib.F64, self._st()), "assx_ntf_iterate")
 
     # ------------------------------------------------------------------ LDPSDTF (algorithm/psdtf.py)
     def _psdtf_dims(self, V, H, X=None, ws=None, status=None):
-        """Sizes of a PSDTF call, with every array checked against them (the kernels take pointers and sizes: an array of
-        another shape would be read past its end).  Refused with ValueError before any launch."""
         if self.prec.code != _lib.F64:
             raise ValueError("LDPSDTF supports float64 only")
         if V.dim() != 4 or H.dim() != 3 or V.shape[2] != V.shape[3]:
@@ -721,38 +705,23 @@ class Engine:
             raise ValueError("LDPSDTF: n_bins must be in [1, 64], got %d" % M)
         if B < 1 or T < 1:
             raise ValueError("LDPSDTF: empty problem B=%d T=%d" % (B, T))
-        want = {"basis": (V, (B, K, M, M)), "activation": (H, (B, K, T))}
-        if X is not None:
-            want["target"] = (X, (B, T, M, M))
-        for name, (a, shape) in want.items():
-            self._psdtf_array(a, shape, name)
+        self._args("LDPSDTF", (("basis", V, (B, K, M, M), torch.float64), ("activation", H, (B, K, T), torch.float64),
+                               ("target", X, (B, T, M, M), torch.float64)))
         if ws is not None:
-            need = self._L.assx_psdtf_workspace_bytes(B, M, T, K, _lib.F64)
-            if need == 0 or ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need:
-                raise ValueError("LDPSDTF: workspace of %d bytes, %d needed for B=%d M=%d T=%d K=%d"
-                                 % (ws.numel(), need, B, M, T, K))
-        if status is not None:
-            self._psdtf_array(status, (B,), "status", torch.int32)
+            check_workspace("LDPSDTF", ws, self.dev, self._L.assx_psdtf_workspace_bytes(B, M, T, K, _lib.F64))
+        self._arg("LDPSDTF", "status", status, torch.int32, (B,))
         return B, M, T, K
 
-    def _psdtf_array(self, a, shape, name, dtype=torch.float64):
-        if a.dtype != dtype or a.device != self.dev:
-            raise ValueError("LDPSDTF: %s must be %s on %s, got %s on %s" % (name, dtype, self.dev, a.dtype, a.device))
-        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
-            raise ValueError("LDPSDTF: %s has shape %s, needs %s (contiguous)" % (name, tuple(a.shape), tuple(shape)))
-
     def psdtf_workspace(self, B, M, T, K):
-        n = self._L.assx_psdtf_workspace_bytes(B, M, T, K, self.prec.code)
-        if n == 0:
-            raise ValueError("LDPSDTF supports float64, 1 <= n_bins <= 64 and 1 <= n_basis <= 64; got dtype=%s, "
-                             "n_bins=%d, n_basis=%d" % (self.prec.name, M, K))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_psdtf_workspace_bytes(B, M, T, K, self.prec.code),
+                                   "LDPSDTF supports float64, 1 <= n_bins <= 64 and 1 <= n_basis <= 64; got dtype=%s, "
+                                   "n_bins=%d, n_basis=%d", self.prec.name, M, K)
 
     def psdtf_to_psd(self, A, eps=1e-12):
         """to_PSD of (n, M, M) symmetric matrices, in place."""
         if A.dim() != 3 or A.shape[1] != A.shape[2] or not 1 <= int(A.shape[1]) <= 64 or int(A.shape[0]) < 1:
             raise ValueError("psdtf_to_psd: expected (n, M, M) with 1 <= M <= 64, got %s" % (tuple(A.shape),))
-        self._psdtf_array(A, tuple(A.shape), "A")
+        self._arg("LDPSDTF", "A", A, torch.float64, A.shape)
         self._check(self._L.assx_psdtf_to_psd(self.ctx, ptr(A), int(A.shape[0]), int(A.shape[1]), float(eps), self._st()),
                     "assx_psdtf_to_psd")
         return A
@@ -782,7 +751,7 @@ class Engine:
         """loss (B,) float64: the log-det divergence of the model as it stands, summed over the frames."""
         B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
         loss = loss if loss is not None else self.empty((B,), dtype=torch.float64)
-        self._psdtf_array(loss, (B,), "loss")
+        self._arg("LDPSDTF", "loss", loss, torch.float64, (B,))
         self._check(self._L.assx_psdtf_loss(self.ctx, ptr(X), ptr(V), ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), B,
                                             M, T, K, _lib.F64, self._st()), "assx_psdtf_loss")
         return loss
@@ -791,7 +760,7 @@ class Engine:
         """(B,T,M,M): sum_k H V_k."""
         B, M, T, K = self._psdtf_dims(V, H)
         Xh = out if out is not None else self.empty((B, T, M, M), dtype=torch.float64)
-        self._psdtf_array(Xh, (B, T, M, M), "out")
+        self._arg("LDPSDTF", "out", Xh, torch.float64, (B, T, M, M))
         self._check(self._L.assx_psdtf_reconstruct(self.ctx, ptr(V), ptr(H), ptr(Xh), B, M, T, K, _lib.F64, self._st()),
                     "assx_psdtf_reconstruct")
         return Xh
@@ -801,28 +770,24 @@ class Engine:
         B, M, T, K = self._psdtf_dims(V, H, X, ws, status)
         if int(n_iter) < 0:
             raise ValueError("LDPSDTF: n_iter must be >= 0, got %d" % int(n_iter))
-        if loss is not None:
-            self._psdtf_array(loss, (int(n_iter), B), "loss")
+        self._arg("LDPSDTF", "loss", loss, torch.float64, (int(n_iter), B))
         self._check(self._L.assx_psdtf_iterate(self.ctx, int(n_iter), ptr(X), ptr(V), ptr(H), float(eps),
                                                int(bool(normalize)), ptr(loss), ptr(status), ptr(ws), B, M, T, K, _lib.F64,
                                                self._st()), "assx_psdtf_iterate")
 
     # ------------------------------------------------------------------ GaussIPSDTA (include/assx.h (f10))
+    _IPSDTA_SUPPORTS = ("%s supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
+                        "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
+                        "n_blocks=%d")
+
     @staticmethod
     def ipsdta_packed_size(F, n_blocks):
         """P: the entries of one packed basis (the nb x nb blocks end to end)."""
         nn, rem = F // n_blocks, F % n_blocks
         return (n_blocks - rem) * nn * nn + rem * (nn + 1) * (nn + 1)
 
-    def _ipsdta_array(self, a, shape, name, dtype, model="GaussIPSDTA"):
-        if a.dtype != dtype or a.device != self.dev:
-            raise ValueError("%s: %s must be %s on %s, got %s on %s" % (model, name, dtype, self.dev, a.dtype, a.device))
-        if tuple(a.shape) != tuple(shape) or not a.is_contiguous():
-            raise ValueError("%s: %s has shape %s, needs %s (contiguous)" % (model, name, tuple(a.shape), tuple(shape)))
-
     def _ipsdta_dims(self, n_blocks, U, H, X=None, W=None, ws=None, status=None, nu=None):
-        """Shapes are checked here, where they are still known: the C-ABI takes pointers and sizes.  nu: None for (f10),
-        the degree of freedom for (f11), whose workspace is then the one checked."""
+        """nu: None for (f10), the degree of freedom for (f11), whose workspace is then the one checked."""
         model = "GaussIPSDTA" if nu is None else "tIPSDTA"
         if U.dim() != 3 or H.dim() != 3:
             raise ValueError("%s: packed basis (N, K, P) and activation (N, K, T) expected, got %s and %s"
@@ -837,62 +802,54 @@ class Engine:
         n_blocks = int(n_blocks)
         need = self._L.assx_ipsdta_workspace_bytes(M, F, T, K, n_blocks, self.prec.code)
         if need == 0:
-            raise ValueError("%s supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
-                             "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
-                             "n_blocks=%d" % (model, self.prec.name, M, F, T, K, n_blocks))
-        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, n_blocks)), "basis", torch.complex128, model)
-        self._ipsdta_array(H, (M, K, T), "activation", torch.float64, model)
-        if X is not None:
-            self._ipsdta_array(X, (M, F, T), "input", torch.complex128, model)
-        if W is not None:
-            self._ipsdta_array(W, (F, M, M), "demix_filter", torch.complex128, model)
-        if status is not None:
-            self._ipsdta_array(status, (1,), "status", torch.int32, model)
+            raise ValueError(self._IPSDTA_SUPPORTS % (model, self.prec.name, M, F, T, K, n_blocks))
+        self._args(model, (("basis", U, (M, K, self.ipsdta_packed_size(F, n_blocks)), torch.complex128),
+                           ("activation", H, (M, K, T), torch.float64), ("input", X, (M, F, T), torch.complex128),
+                           ("demix_filter", W, (F, M, M), torch.complex128), ("status", status, (1,), torch.int32)))
         if nu is not None:
             nu = float(nu)
             if not 0.0 < nu < float("inf"):
                 raise ValueError("tIPSDTA: nu must be finite and > 0, got %r" % (nu,))
             need = self._L.assx_tipsdta_workspace_bytes(M, F, T, K, n_blocks, self.prec.code, nu)
-        if ws is not None and (ws.dtype != torch.uint8 or ws.device != self.dev or ws.numel() < need):
-            raise ValueError("%s: workspace of %d bytes, %d needed" % (model, ws.numel(), need))
+        if ws is not None:
+            check_workspace(model, ws, self.dev, need)
         return M, F, T, K, n_blocks
 
     def _ipsdta_call(self, entry, nu, X, W, U, H, ws, n_blocks, eps, status, lead=(), mid=(), counts=None, loss=None):
         """The dims check and the call of assx_ipsdta_<entry> (nu None) or assx_tipsdta_<entry>: `lead` goes before X, nu
-        after eps, `mid` after nu.  counts: (message, values) of the arguments that must be >= 0; loss: (array, shape)."""
+        after eps, `mid` after nu.  counts: (message, values) of the arguments that must be >= 0; loss: (array or None,
+        shape) where the entry takes a loss, whose pointer then follows `mid`."""
         model, name = ("GaussIPSDTA", "assx_ipsdta_" + entry) if nu is None else ("tIPSDTA", "assx_tipsdta_" + entry)
         M, F, T, K, nb = self._ipsdta_dims(n_blocks, U, H, X, W, ws, status, nu)
         if counts is not None and min(counts[1]) < 0:
             raise ValueError("%s: %s must be >= 0, got %s" % (model, counts[0], " and ".join("%d" % v for v in counts[1])))
         if loss is not None:
-            self._ipsdta_array(loss[0], loss[1], "loss", torch.float64, model)
+            self._arg(model, "loss", loss[0], torch.float64, loss[1])
+            mid = tuple(mid) + (ptr(loss[0]),)
         args = tuple(lead) + (ptr(X), ptr(W), ptr(U), ptr(H), float(eps)) + (() if nu is None else (float(nu),)) + tuple(mid)
         self._check(getattr(self._L, name)(self.ctx, *args, ptr(status), ptr(ws), M, F, T, K, nb, _lib.F64, self._st()), name)
 
     def _ipsdta_loss(self, nu, X, W, U, H, ws, n_blocks, eps, loss, status):
         loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
-        self._ipsdta_call("loss", nu, X, W, U, H, ws, n_blocks, eps, status, mid=(ptr(loss),), loss=(loss, (1,)))
+        self._ipsdta_call("loss", nu, X, W, U, H, ws, n_blocks, eps, status, loss=(loss, (1,)))
         return loss
 
     def _ipsdta_iterate(self, nu, n_iter, spatial_iteration, X, W, U, H, ws, n_blocks, eps, normalize, loss, status):
         n_iter, sp = int(n_iter), int(spatial_iteration)
         self._ipsdta_call("iterate", nu, X, W, U, H, ws, n_blocks, eps, status, lead=(n_iter, sp),
-                          mid=(int(bool(normalize)), ptr(loss)), counts=("n_iter and spatial_iteration", (n_iter, sp)),
-                          loss=None if loss is None else (loss, (n_iter,)))
+                          mid=(int(bool(normalize)),), counts=("n_iter and spatial_iteration", (n_iter, sp)),
+                          loss=(loss, (n_iter,)))
 
     def ipsdta_workspace(self, M, F, T, K, n_blocks):
-        n = self._L.assx_ipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code)
-        if n == 0:
-            raise ValueError("GaussIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins "
-                             "and blocks of at most 8 bins; got dtype=%s, n_channels=%d, n_bins=%d, n_frames=%d, n_basis=%d, "
-                             "n_blocks=%d" % (self.prec.name, M, F, T, K, n_blocks))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_ipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks),
+                                                                       self.prec.code),
+                                   self._IPSDTA_SUPPORTS, "GaussIPSDTA", self.prec.name, M, F, T, K, n_blocks)
 
     def ipsdta_to_psd(self, A, eps=1e-12):
         """to_PSD of (n, nb, nb) Hermitian matrices, in place."""
         if A.dim() != 3 or A.shape[1] != A.shape[2] or not 1 <= int(A.shape[1]) <= 8 or int(A.shape[0]) < 1:
             raise ValueError("ipsdta_to_psd: expected (n, nb, nb) with 1 <= nb <= 8, got %s" % (tuple(A.shape),))
-        self._ipsdta_array(A, tuple(A.shape), "A", torch.complex128)
+        self._arg("GaussIPSDTA", "A", A, torch.complex128, A.shape)
         self._check(self._L.assx_ipsdta_to_psd(self.ctx, ptr(A), int(A.shape[0]), int(A.shape[1]), float(eps), self._st()),
                     "assx_ipsdta_to_psd")
         return A
@@ -911,8 +868,8 @@ class Engine:
         F, nb = int(n_bins), int(n_blocks)
         if self._L.assx_ipsdta_workspace_bytes(M, F, T, K, nb, self.prec.code) == 0:
             raise ValueError("GaussIPSDTA: n_channels=%d n_bins=%d n_basis=%d n_blocks=%d outside the envelope" % (M, F, K, nb))
-        self._ipsdta_array(U, (M, K, self.ipsdta_packed_size(F, nb)), "basis", torch.complex128)
-        self._ipsdta_array(H, (M, K, T), "activation", torch.float64)
+        self._args("GaussIPSDTA", (("basis", U, (M, K, self.ipsdta_packed_size(F, nb)), torch.complex128),
+                                   ("activation", H, (M, K, T), torch.float64)))
         self._check(self._L.assx_ipsdta_normalize(self.ctx, ptr(U), ptr(H), M, F, T, K, nb, _lib.F64, self._st()),
                     "assx_ipsdta_normalize")
 
@@ -934,12 +891,12 @@ class Engine:
 
     # ------------------------------------------------------------------ tIPSDTA (include/assx.h (f11))
     def tipsdta_workspace(self, M, F, T, K, n_blocks, nu=1.0):
-        n = self._L.assx_tipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks), self.prec.code, float(nu))
-        if n == 0:
-            raise ValueError("tIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= n_bins, "
-                             "blocks of at most 8 bins and a finite nu > 0; got dtype=%s, n_channels=%d, n_bins=%d, "
-                             "n_frames=%d, n_basis=%d, n_blocks=%d, nu=%r" % (self.prec.name, M, F, T, K, n_blocks, nu))
-        return torch.empty(int(n), dtype=torch.uint8, device=self.dev)
+        return self._new_workspace(self._L.assx_tipsdta_workspace_bytes(int(M), int(F), int(T), int(K), int(n_blocks),
+                                                                        self.prec.code, float(nu)),
+                                   "tIPSDTA supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64, 1 <= n_blocks <= "
+                                   "n_bins, blocks of at most 8 bins and a finite nu > 0; got dtype=%s, n_channels=%d, "
+                                   "n_bins=%d, n_frames=%d, n_basis=%d, n_blocks=%d, nu=%r",
+                                   self.prec.name, M, F, T, K, n_blocks, nu)
 
     def tipsdta_update_basis(self, X, W, U, H, ws, n_blocks, nu=1.0, eps=1e-12, status=None):
         self._ipsdta_call("update_basis", nu, X, W, U, H, ws, n_blocks, eps, status)
@@ -972,7 +929,7 @@ class Engine:
             if a.dtype != torch.complex128 or a.device != self.dev or not a.is_contiguous():
                 raise ValueError("hermitian_riccati: A and B must be contiguous complex128 on %s" % self.dev)
         n, M = int(A.shape[0]), int(A.shape[1])
-        self._fastmnmf_need(status, n, "status")
+        self._arg("hermitian_riccati", "status", status, torch.int32, numel=n)
         H = self.empty((n, M, M), dtype=torch.complex128)
         self._check(self._L.assx_hermitian_riccati(self.ctx, ptr(A), ptr(Bm), ptr(H), ptr(status), n, M, _lib.F64,
                                                    self._st()), "assx_hermitian_riccati")
