@@ -117,6 +117,13 @@ SIGNATURES = {
     "assx_tipsdta_update_spatial": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_tipsdta_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "assx_tipsdta_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "assx_covnmf_update_basis": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_update_activation": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_update_spatial": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_covnmf_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -7,6 +7,9 @@ kernels (include/assx.h: assx_nmf_update / assx_nmf_loss); there is no CPU fallb
 
 `ComplexEUCNMF` (nmf.py:58-114, 597-676) returns `(basis.copy(), activation.copy(), phase.copy())` and runs on
 assx_cnmf_update / assx_cnmf_iterate.
+
+`MultichannelISNMF` (nmf.py:116-148, 678-815), multichannel IS-NMF on a tensor of Hermitian covariance matrices, returns
+`(spatial.copy(), basis.copy(), activation.copy())` and runs on assx_covnmf_* (include/assx.h (f12)).
 """
 import numpy as np
 
@@ -454,3 +457,208 @@ class ComplexEUCNMF(ComplexNMFbase):
         self._touch("T", "V", "Phi")
 
         self.update_beta()
+
+
+class MultichannelNMFbase(DeviceState):
+    """reference: nmf.py:116-148.  Keyword arguments of the call become attributes; `loss`, created once by the
+    constructor, is never cleared between calls."""
+
+    N_BASIS_MAX = 64
+
+    def __init__(self, n_basis=2, eps=EPS, *, dtype='float64', device=None):
+        """
+        Args:
+            n_basis: number of basis
+        """
+        if str(dtype) not in ('float64', 'double', 'complex128'):
+            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+
+        self.n_basis = n_basis
+        self.loss = LazyLossList()
+
+        self.eps = eps
+
+        self.dtype = 'float64'
+        self.device = device
+        self._engine = None
+
+    def __call__(self, target, iteration=100, **kwargs):
+        self.target = target
+
+        self._reset(**kwargs)
+
+        self.update(iteration=iteration)
+
+    def _reset(self, **kwargs):
+        assert self.target is not None, "Specify data!"
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+    def update(self, iteration=100):
+        raise NotImplementedError("Implement `update` method.")
+
+    def update_once(self):
+        raise NotImplementedError("Implement `update_once` method.")
+
+
+class MultichannelISNMF(MultichannelNMFbase):
+    """reference: nmf.py:678-815 ("Multichannel Extensions of Non-Negative Matrix Factorization With Complex-Valued
+    Data"), multichannel IS-NMF on a tensor of Hermitian covariance matrices: target[f,t] ~ sum_k basis[f,k]
+    activation[k,t] spatial[f,k].  float64 / complex128, one target (n_bins, n_frames, n_channels, n_channels),
+    2 <= n_channels <= 8, 1 <= n_basis <= 64.  `update_once()` and its parts run as HIP kernels (include/assx.h (f12):
+    assx_covnmf_*); the loop of `update()` is one call of assx_covnmf_iterate.  There is no CPU fallback.
+
+    Not to be confused with bss.mnmf.MultichannelISNMF (Sawada's MNMF with a latent assignment, on a mixture
+    (n_channels, n_bins, n_frames)).  Deviations from the reference: `spatial` is always complex128 (the reference
+    starts it as a real identity), and there is no `criterion` attribute (the loss is computed on the device; it needs a
+    positive-definite target).  The target and `spatial` are read as Hermitian matrices.  A point whose model
+    covariance is not positive definite where the method inverts it raises numpy.linalg.LinAlgError at the end of the
+    call, not in the middle."""
+    spatial = DeviceArray("H", complex_=True)
+    basis = DeviceArray("T", complex_=False)
+    activation = DeviceArray("V", complex_=False)
+
+    N_CHANNELS_MIN, N_CHANNELS_MAX = 2, 8
+
+    def __init__(self, n_basis=10, normalize=True, eps=EPS, *, dtype='float64', device=None):
+        """
+        Args:
+            n_basis
+            eps <float>: Machine epsilon
+        """
+        super().__init__(n_basis=n_basis, eps=eps, dtype=dtype, device=device)
+
+        self.normalize = normalize
+
+    def __call__(self, target, iteration=100, **kwargs):
+        """
+        Args:
+            target <np.ndarray>: (n_bins, n_frames, n_channels, n_channels), complex Hermitian
+            iteration <int>: Default: 100
+        Returns:
+            spatial (n_bins, n_basis, n_channels, n_channels), basis (n_bins, n_basis), activation (n_basis, n_frames)
+        """
+        self.target = target
+
+        self._reset(**kwargs)
+
+        self.update(target, iteration=iteration)
+
+        H, T, V = self.spatial, self.basis, self.activation
+
+        return H.copy(), T.copy(), V.copy()
+
+    def _reset(self, **kwargs):
+        """Everything of nmf.py:705-728: the refusals first, then the device and the draws."""
+        super()._reset(**kwargs)
+
+        target = self.target
+        name = type(self).__name__
+        n_basis = self.n_basis
+        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
+            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        is_tensor = isinstance(target, torch.Tensor)
+        if not (target.is_complex() if is_tensor else np.iscomplexobj(target)):
+            raise ValueError("{} supports complex targets only".format(name))
+        shape = tuple(int(s) for s in target.shape) if hasattr(target, "shape") else np.shape(target)
+        if len(shape) != 4:
+            raise ValueError("target must be (n_bins, n_frames, n_channels, n_channels), got {} dims".format(len(shape)))
+        n_bins, n_frames, n_channels, _n_channels = shape
+        if _n_channels != n_channels:
+            raise ValueError("target must be square in its last two axes, got shape {}".format(shape))
+        if not self.N_CHANNELS_MIN <= n_channels <= self.N_CHANNELS_MAX:
+            raise ValueError("n_channels must be in [{}, {}], got {}".format(self.N_CHANNELS_MIN, self.N_CHANNELS_MAX,
+                                                                             n_channels))
+        if n_bins < 1 or n_frames < 1:
+            raise ValueError("target must not be empty, got shape {}".format(shape))
+        for attr, want in (("spatial", (n_bins, n_basis, n_channels, n_channels)), ("basis", (n_bins, n_basis)),
+                           ("activation", (n_basis, n_frames))):
+            if hasattr(self, attr):
+                a = getattr(self, attr)
+                if attr != "spatial" and np.iscomplexobj(a):
+                    raise ValueError("{} supports a real {} only".format(name, attr))
+                if tuple(a.shape) != want:
+                    raise ValueError("{} has shape {}, the target needs {}".format(attr, tuple(a.shape), want))
+
+        self.n_bins, self.n_frames = n_bins, n_frames
+        self.n_channels = n_channels
+
+        eng = self._ensure_engine()
+        self._batched = False
+        self._X = to_device(target, torch.complex128, eng.dev).contiguous()
+        self._ws = eng.covnmf_workspace(n_channels, n_bins, n_frames, n_basis)
+        self._status = eng.new_status(1)
+
+        if not hasattr(self, 'spatial'):
+            H = np.eye(n_channels, dtype=np.complex128)
+            self.spatial = np.tile(H, reps=(n_bins, n_basis, 1, 1))
+        else:
+            self.spatial = np.array(self.spatial, dtype=np.complex128)
+        if not hasattr(self, 'basis'):
+            self.basis = np.random.rand(n_bins, n_basis)
+        else:
+            self.basis = np.array(self.basis, dtype=np.float64)
+        if not hasattr(self, 'activation'):
+            self.activation = np.random.rand(n_basis, n_frames)
+        else:
+            self.activation = np.array(self.activation, dtype=np.float64)
+
+    def _model(self):
+        """(T (F,K), V (K,T), H (F,K,M,M)) on the device: the tensors of the attributes without their leading axis."""
+        return self._dev("T", False)[0], self._dev("V", False)[0], self._dev("H", True)[0]
+
+    _STEPS = ("update", "update_once", "update_basis", "update_activation", "update_spatial", "reconstruct",
+              "_record_loss")
+
+    def _fast_loop_ok(self):
+        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_covnmf_iterate when every step is this module's."""
+        return self._steps_are(MultichannelISNMF, self._STEPS) and isinstance(self.loss, LazyLossList)
+
+    def _record_loss(self):
+        T, V, H = self._model()
+        loss = self._engine.covnmf_loss(self._X, T, V, H, self._ws, eps=self.eps, status=self._status)
+        append_loss(self.loss, loss, False)
+
+    def update(self, target=None, iteration=100):
+        """nmf.py:730-736; `target` is accepted as there and, as there, the model's own target is what is used."""
+        if self._fast_loop_ok():
+            if iteration > 0:
+                eng = self._engine
+                loss = eng.empty((iteration, 1), dtype=torch.float64)
+                T, V, H = self._model()
+                eng.covnmf_iterate(iteration, self._X, T, V, H, self._ws, normalize=self.normalize, eps=self.eps,
+                                   loss=loss, status=self._status)
+                self._touch("T", "V", "H")
+                self.loss.append_device_block(loss, False)
+        else:
+            for idx in range(iteration):
+                self.update_once()
+
+                self._record_loss()
+        self._check_status()
+
+    def update_once(self):
+        self.update_basis()
+        self.update_activation()
+        self.update_spatial()
+
+    def update_basis(self):
+        T, V, H = self._model()
+        self._engine.covnmf_update_basis(self._X, T, V, H, self._ws, eps=self.eps, status=self._status)
+        self._touch("T")
+
+    def update_activation(self):
+        T, V, H = self._model()
+        self._engine.covnmf_update_activation(self._X, T, V, H, self._ws, eps=self.eps, status=self._status)
+        self._touch("V")
+
+    def update_spatial(self):
+        T, V, H = self._model()
+        self._engine.covnmf_update_spatial(self._X, T, V, H, self._ws, normalize=self.normalize, eps=self.eps,
+                                           status=self._status)
+        self._touch("H")
+
+    def reconstruct(self):
+        """sum_k spatial * basis * activation, (n_bins, n_frames, n_channels, n_channels) complex."""
+        return to_numpy(self._engine.covnmf_reconstruct(*self._model()), np.complex128)

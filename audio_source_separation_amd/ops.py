@@ -18,8 +18,8 @@ _RAW = _lib.lib
 # The C-ABI takes pointers and sizes, and its kernels write float64, int32 or the model's own type through them.  An
 # array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
 # batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
-# read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF and the
-# two IPSDTA models passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF, the
+# two IPSDTA models and the covariance-domain MNMF passes one of the two checks below, where all of that is still known, and is refused with ValueError
 # before anything is launched.
 def check_array(model, name, a, dtype, device, shape=None, numel=None):
     """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
@@ -400,7 +400,7 @@ class Engine:
                     "assx_fastmnmf_update_diagonalizer")
         return Q
 
-    # ------------------------------------------------------------------ the six factorisation model families
+    # ------------------------------------------------------------------ the seven factorisation model families
     # Every array and workspace goes through check_array / check_workspace (top of this module) before its address does
     # through ptr().  A `_X_dims` holds only what is its family's own: how the sizes are read off the arrays, the range
     # limits, the arrays wanted as (name, array, shape, dtype), the workspace query.
@@ -934,6 +934,68 @@ class Engine:
         self._check(self._L.assx_hermitian_riccati(self.ctx, ptr(A), ptr(Bm), ptr(H), ptr(status), n, M, _lib.F64,
                                                    self._st()), "assx_hermitian_riccati")
         return H
+
+    # ------------------------------------------------------------------ covariance-domain MultichannelISNMF (algorithm/nmf.py)
+    def _covnmf_dims(self, Tb, V, H, X=None, ws=None, status=None):
+        if Tb.dim() != 2 or V.dim() != 2 or H.dim() != 4:
+            raise ValueError("CovNMF: expected basis (F,K), activation (K,T) and spatial (F,K,M,M), got %s, %s and %s"
+                             % (tuple(Tb.shape), tuple(V.shape), tuple(H.shape)))
+        F, K = (int(d) for d in Tb.shape)
+        M, T = int(H.shape[-1]), int(V.shape[-1])
+        self._args("CovNMF", (("target", X, (F, T, M, M), torch.complex128), ("basis", Tb, (F, K), torch.float64),
+                              ("activation", V, (K, T), torch.float64), ("spatial", H, (F, K, M, M), torch.complex128)))
+        self._arg("CovNMF", "status", status, torch.int32, numel=1)
+        if ws is not None:
+            check_workspace("CovNMF", ws, self.dev, self._L.assx_covnmf_workspace_bytes(M, F, T, K, _lib.F64))
+        return M, F, T, K
+
+    def covnmf_workspace(self, M, F, T, K):
+        return self._new_workspace(self._L.assx_covnmf_workspace_bytes(M, F, T, K, _lib.F64),
+                                   "CovNMF supports float64, 2 <= n_channels <= 8, 1 <= n_basis <= 64 and a target below "
+                                   "4 GiB; got n_channels=%d, n_basis=%d, n_bins=%d, n_frames=%d", M, K, F, T)
+
+    def _covnmf_step(self, what, X, Tb, V, H, ws, eps, status):
+        M, F, T, K = self._covnmf_dims(Tb, V, H, X, ws, status)
+        self._check(getattr(self._L, what)(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(H), float(eps), ptr(status), ptr(ws), M,
+                                           F, T, K, _lib.F64, self._st()), what)
+
+    def covnmf_update_basis(self, X, Tb, V, H, ws, eps=1e-12, status=None):
+        self._covnmf_step("assx_covnmf_update_basis", X, Tb, V, H, ws, eps, status)
+
+    def covnmf_update_activation(self, X, Tb, V, H, ws, eps=1e-12, status=None):
+        self._covnmf_step("assx_covnmf_update_activation", X, Tb, V, H, ws, eps, status)
+
+    def covnmf_update_spatial(self, X, Tb, V, H, ws, normalize=True, eps=1e-12, status=None):
+        M, F, T, K = self._covnmf_dims(Tb, V, H, X, ws, status)
+        self._check(self._L.assx_covnmf_update_spatial(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(H), 1 if normalize else 0,
+                                                       float(eps), ptr(status), ptr(ws), M, F, T, K, _lib.F64,
+                                                       self._st()), "assx_covnmf_update_spatial")
+
+    def covnmf_reconstruct(self, Tb, V, H, out=None):
+        """(F,T,M,M) complex128 = sum_k Tb V H_k."""
+        M, F, T, K = self._covnmf_dims(Tb, V, H)
+        Xh = out if out is not None else self.empty((F, T, M, M), dtype=torch.complex128)
+        self._arg("CovNMF", "out", Xh, torch.complex128, shape=(F, T, M, M))
+        self._check(self._L.assx_covnmf_reconstruct(self.ctx, ptr(Tb), ptr(V), ptr(H), ptr(Xh), M, F, T, K, _lib.F64,
+                                                    self._st()), "assx_covnmf_reconstruct")
+        return Xh
+
+    def covnmf_loss(self, X, Tb, V, H, ws, eps=1e-12, loss=None, status=None):
+        """loss (1,) float64: the multichannel Itakura-Saito divergence of the model as it stands."""
+        M, F, T, K = self._covnmf_dims(Tb, V, H, X, ws, status)
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._arg("CovNMF", "loss", loss, torch.float64, numel=1)
+        self._check(self._L.assx_covnmf_loss(self.ctx, ptr(X), ptr(Tb), ptr(V), ptr(H), float(eps), ptr(loss), ptr(status),
+                                             ptr(ws), M, F, T, K, _lib.F64, self._st()), "assx_covnmf_loss")
+        return loss
+
+    def covnmf_iterate(self, n_iter, X, Tb, V, H, ws, normalize=True, eps=1e-12, loss=None, status=None):
+        """n_iter x (basis, activation, spatial, loss); loss: (n_iter,) float64 or None."""
+        M, F, T, K = self._covnmf_dims(Tb, V, H, X, ws, status)
+        self._arg("CovNMF", "loss", loss, torch.float64, numel=max(int(n_iter), 1))
+        self._check(self._L.assx_covnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Tb), ptr(V),
+                                                ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), M, F, T, K, _lib.F64,
+                                                self._st()), "assx_covnmf_iterate")
 
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):

@@ -561,6 +561,38 @@ int assx_tipsdta_iterate(assx_ctx* ctx, int n_iter, int spatial_iteration, const
                          double nu, int normalize, double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M,
                          int F, int T, int K, int n_blocks, int dtype, void* stream);
 
+/* ---- (f12) MultichannelISNMF in the covariance domain (src/algorithm/nmf.py:116-148, 678-815) -----------------------------
+ * X[f,t] ~ sum_k Tb[f,k] V[k,t] H[f,k] for a target of Hermitian M x M matrices.  State: X (F,T,M,M) complex128 (read as
+ * Hermitian: its lower triangle in the loss, whole rows elsewhere), Tb (F,K), V (K,T) float64, H (F,K,M,M) complex128
+ * (Hermitian, read from its lower triangle).  One target, no batch axis; `status` is one word.  Envelope: ASSX_F64,
+ * 2 <= M <= 8, 1 <= K <= 64, F, T >= 1, M M F T < 2^28 (ASSX_E_UNSUPPORTED outside).  `ws` (assx_covnmf_workspace_bytes; 0
+ * outside the envelope, no GPU needed) is scratch: 8 (2 K F T + 2 M^2 F T + ..) bytes.  Every step re-forms
+ * X^ = sum_k Tb V H_k, P = (X^ + eps I)^-1 and Q = P X P from the parameters as they stand; a point whose X^ + eps I has
+ * no Cholesky factor sets ASSX_STATUS_SINGULAR.
+ *   assx_covnmf_update_basis       nmf.py:743-762: Tb *= sqrt(sum_t V tr(Q H_k) / max(sum_t V tr(P H_k), eps)).
+ *   assx_covnmf_update_activation  nmf.py:764-783: V *= sqrt(sum_f Tb tr(Q H_k) / max(sum_f Tb tr(P H_k), eps)).
+ *   assx_covnmf_update_spatial     nmf.py:785-806: A = sum_t V P, B = H (sum_t V Q) H, H <- the solution of H A H = B (closed
+ *                                  form; H = 0 where A is exactly 0), + eps I, / trace if `normalize`.
+ *   assx_covnmf_reconstruct        Xh (F,T,M,M) = sum_k Tb V H_k, entry by entry.
+ *   assx_covnmf_loss               loss[0] = sum_{f,t} tr((X + eps I) P) - ln det(X + eps I) + ln det(X^ + eps I) - M, both
+ *                                  log-determinants from Cholesky factors (a failed one sets ASSX_STATUS_SINGULAR).
+ *   assx_covnmf_iterate            n_iter x (basis, activation, spatial, then loss into loss[i] if loss != NULL), enqueued
+ *                                  without a synchronisation, bit for bit the single calls. */
+size_t assx_covnmf_workspace_bytes(int M, int F, int T, int K, int dtype);
+int assx_covnmf_update_basis(assx_ctx* ctx, const void* X, void* Tb, const void* V, const void* H, double eps,
+                             int32_t* status, void* ws, int M, int F, int T, int K, int dtype, void* stream);
+int assx_covnmf_update_activation(assx_ctx* ctx, const void* X, const void* Tb, void* V, const void* H, double eps,
+                                  int32_t* status, void* ws, int M, int F, int T, int K, int dtype, void* stream);
+int assx_covnmf_update_spatial(assx_ctx* ctx, const void* X, const void* Tb, const void* V, void* H, int normalize,
+                               double eps, int32_t* status, void* ws, int M, int F, int T, int K, int dtype, void* stream);
+int assx_covnmf_reconstruct(assx_ctx* ctx, const void* Tb, const void* V, const void* H, void* Xh /* (F,T,M,M) complex */,
+                            int M, int F, int T, int K, int dtype, void* stream);
+int assx_covnmf_loss(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const void* H, double eps,
+                     double* loss /* (1,) */, int32_t* status, void* ws, int M, int F, int T, int K, int dtype, void* stream);
+int assx_covnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* X, void* Tb, void* V, void* H, double eps,
+                        double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M, int F, int T, int K,
+                        int dtype, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
