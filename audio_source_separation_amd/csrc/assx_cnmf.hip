@@ -29,7 +29,7 @@
 // is off for the whole file: with one basis and a silent entry Zbar = a E + 1 (0 - a E) must come out exactly 0 (the
 // reference's angle there is 0), which fma(a, E, -round(a E)) is not.
 #include "assx_common.hpp"
-#include "assx_mnmf_common.hpp"
+#include "assx_factor_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -40,17 +40,13 @@ using mf::KMAX;
 using mf::block_pair_sums;
 using mf::block_sum;
 using mf::nblocks;
+using mf::strided_sum;
 
 namespace {
 
 constexpr int NW = BLK / WAVE;  // waves of a workgroup
 constexpr int FS_MAX = 32;      // bin slabs of the activation pass, at least 8 bins each
 enum { REG_RCP = 0, REG_ONE = 1, REG_POW = 2 };  // Vf^(p-2) for p = 1, p = 2, any other p
-
-inline int cn_slabs(int F) {
-  const int s = (F + 7) / 8;
-  return s > FS_MAX ? FS_MAX : s;
-}
 
 struct CnLayout {
   size_t zx, tvs, tnew, lossp, part, total;
@@ -60,13 +56,14 @@ struct CnLayout {
 // part: slab partials of the activation sums (B,FS,2,K,T).  All float64.
 CnLayout cn_layout(int B, int F, int T, int K) {
   const size_t d = sizeof(double), bft = (size_t)B * F * T;
+  mf::Carve c(256);
   CnLayout L;
-  L.zx = 0;
-  L.tvs = align_up(L.zx + 2 * bft * d, 256);
-  L.tnew = align_up(L.tvs + bft * d, 256);
-  L.lossp = align_up(L.tnew + (size_t)B * F * K * d, 256);
-  L.part = align_up(L.lossp + (size_t)B * F * d, 256);
-  L.total = align_up(L.part + (size_t)B * cn_slabs(F) * 2 * K * T * d, 256);
+  L.zx = c.take(2 * bft * d);
+  L.tvs = c.take(bft * d);
+  L.tnew = c.take((size_t)B * F * K * d);
+  L.lossp = c.take((size_t)B * F * d);
+  L.part = c.take((size_t)B * mf::slabs8(F, FS_MAX) * 2 * K * T * d);
+  L.total = c.total();
   return L;
 }
 
@@ -232,19 +229,6 @@ __global__ void __launch_bounds__(BLK) cn_act_kernel(const double* __restrict__ 
   }
 }
 
-// the sum of n values in a fixed order: every thread its stride, then the workgroup; thread 0 returns it
-__device__ __forceinline__ double cn_strided_sum(const double* __restrict__ p, int n, size_t stride, double* red) {
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += BLK) v += p[(size_t)i * stride];
-  return block_sum<double, NW>(v, red);
-}
-
-__global__ void __launch_bounds__(BLK) cn_loss_kernel(const double* __restrict__ lossp, double* __restrict__ loss, int F) {
-  __shared__ double red[NW];
-  const double tot = cn_strided_sum(lossp + (size_t)blockIdx.x * F, F, 1, red);
-  if (threadIdx.x == 0) loss[blockIdx.x] = tot;
-}
-
 // blocks [0, nvb): V' of 256 (b, k, t) entries each; [nvb, nvb + B K): one basis column each; then B blocks for the
 // loss when loss != NULL
 __global__ void __launch_bounds__(BLK) cn_finalize_kernel(double* __restrict__ Tb, const double* __restrict__ tnew,
@@ -271,7 +255,7 @@ __global__ void __launch_bounds__(BLK) cn_finalize_kernel(double* __restrict__ T
   } else if (blockIdx.x < nvb + (unsigned)(B * K)) {
     const size_t idx = blockIdx.x - nvb, b = idx / K, k = idx % K;
     const double* src = tnew + b * F * K + k;
-    const double tot = cn_strided_sum(src, F, (size_t)K, red);
+    const double tot = strided_sum(src, F, (size_t)K, red);
     if (threadIdx.x == 0) total = tot;
     __syncthreads();
     const double s = total;
@@ -279,7 +263,7 @@ __global__ void __launch_bounds__(BLK) cn_finalize_kernel(double* __restrict__ T
     for (int f = threadIdx.x; f < F; f += BLK) dst[(size_t)f * K] = src[(size_t)f * K] / s;
   } else {
     const size_t b = blockIdx.x - nvb - (unsigned)(B * K);
-    const double tot = cn_strided_sum(lossp + b * F, F, 1, red);
+    const double tot = strided_sum(lossp + b * F, F, 1, red);
     if (threadIdx.x == 0) loss[b] = tot;
   }
 }
@@ -323,7 +307,7 @@ int cn_update(assx_ctx* ctx, const void* X, void* Tb, void* V, void* Phi, double
   hipLaunchKernelGGL(cn_basis_kernel, dim3((unsigned)(B * F)), dim3(BLK), 0, st, (const double*)Tb, (const double*)V,
                      (const double*)Phi, zx, tvs, tnew, eps, F, T, K);
   ASSX_LAUNCH_CHECK(ctx, "cn_basis_kernel");
-  const int FS = cn_slabs(F), nchunk = (K + CH - 1) / CH, ttiles = (int)nblocks((size_t)T, WAVE);
+  const int FS = mf::slabs8(F, FS_MAX), nchunk = (K + CH - 1) / CH, ttiles = (int)nblocks((size_t)T, WAVE);
   hipLaunchKernelGGL(cn_act_kernel, dim3((unsigned)(B * ttiles), (unsigned)(FS * nchunk)), dim3(BLK), 0, st,
                      (const double*)Tb, (const double*)tnew, (const double*)V, (double*)Phi, zx, tvs, part, eps, F, T, K,
                      FS, nchunk, ttiles);
@@ -342,8 +326,9 @@ int cn_loss(assx_ctx* ctx, const void* X, const void* Tb, const void* V, const v
   int rc = cn_resid(ctx, X, Tb, V, Phi, eps, ws, B, F, T, K, st);
   if (rc) return rc;
   const CnLayout L = cn_layout(B, F, T, K);
-  hipLaunchKernelGGL(cn_loss_kernel, dim3((unsigned)B), dim3(BLK), 0, st, (const double*)((char*)ws + L.lossp), loss, F);
-  ASSX_LAUNCH_CHECK(ctx, "cn_loss_kernel");
+  hipLaunchKernelGGL(mf::batch_sum_kernel<false>, dim3((unsigned)B), dim3(BLK), 0, st,
+                     (const double*)((char*)ws + L.lossp), loss, F);
+  ASSX_LAUNCH_CHECK(ctx, "batch_sum_kernel");
   return 0;
 }
 

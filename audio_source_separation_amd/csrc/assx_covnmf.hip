@@ -24,11 +24,11 @@
 //
 // The K reductions per point go through the two trace maps in the workspace, as MNMF's N do: the same evaluation pass
 // serves the basis update (a sum over t) and the activation update (a sum over f), and both sums keep the fixed order
-// of assx_mnmf_common.hpp (wave butterfly, waves in index order, slices in index order; no float atomics).  Two runs
+// of assx_factor_common.hpp (wave butterfly, waves in index order, slices in index order; no float atomics).  Two runs
 // give the same bits, and iterate gives the bits of its steps called one by one.
 #include "assx_common.hpp"
 #include "assx_herm_linalg.hpp"
-#include "assx_mnmf_common.hpp"
+#include "assx_factor_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
@@ -37,14 +37,8 @@ using herm::Mat;
 namespace {
 
 constexpr int EBLK = WAVE;   // threads (frames) of an evaluation workgroup: one wave
-constexpr int SP_SLICES = 8; // t slices of the spatial sums
 constexpr int SBLK = 256;    // threads of a spatial-sum workgroup
 constexpr int MODE_AB = 1, MODE_PQ = 2, MODE_LOSS = 3;
-
-inline int sp_slices(int T) {
-  const int tiles = (T + WAVE - 1) / WAVE;
-  return tiles < SP_SLICES ? tiles : SP_SLICES;
-}
 
 inline bool cv_in_envelope(int M, int F, int T, int K, int dtype) {
   if (dtype != ASSX_F64 || M < 2 || M > 8 || K < 1 || K > KMAX || F < 1 || T < 1) return false;
@@ -60,13 +54,14 @@ struct CvLayout {
 // slice partials (F,S,K,2*M*M); lpart: loss partials (F,nblocks(T, EBLK)).  All float64.
 CvLayout cv_layout(int M, int F, int T, int K) {
   const size_t d = sizeof(double);
+  Carve c(256);
   CvLayout L;
-  L.ab = 0;
-  L.actp = align_up(L.ab + (size_t)2 * K * F * T * d, 256);
-  L.pq = align_up(L.actp + (size_t)act_slices(F) * 2 * K * T * d, 256);
-  L.spp = align_up(L.pq + (size_t)F * T * 2 * M * M * d, 256);
-  L.lpart = align_up(L.spp + (size_t)F * sp_slices(T) * K * 2 * M * M * d, 256);
-  L.total = align_up(L.lpart + (size_t)F * nblocks(T, EBLK) * d, 256);
+  L.ab = c.take((size_t)2 * K * F * T * d);
+  L.actp = c.take((size_t)act_slices(F) * 2 * K * T * d);
+  L.pq = c.take((size_t)F * T * 2 * M * M * d);
+  L.spp = c.take((size_t)F * sp_slices(T) * K * 2 * M * M * d);
+  L.lpart = c.take((size_t)F * nblocks(T, EBLK) * d);
+  L.total = c.total();
   return L;
 }
 
@@ -268,7 +263,8 @@ __global__ void __launch_bounds__(EBLK) cv_eval_kernel(const Cx<double>* __restr
   }
 }
 
-// the loss partials summed in a fixed order by one workgroup
+// the loss partials summed in a fixed order by one workgroup.  Not mf::batch_sum_kernel: with its int count the loop
+// compiles to other code and assx_covnmf_loss measured 6 % slower (profiles/factor_common_refactor_bench.txt)
 __global__ void __launch_bounds__(BLK) cv_loss_finalize_kernel(const double* __restrict__ lpart, double* __restrict__ loss,
                                                                size_t n) {
   __shared__ double red[BLK / WAVE];
@@ -374,20 +370,9 @@ __global__ void __launch_bounds__(SBLK) cv_spatial_sum_kernel(const double* __re
   part[(((size_t)f * S + s) * K + k) * MM2 + e] = acc;
 }
 
-template <int M>
-__device__ __forceinline__ void unpack_herm(const double* p, Mat<M>& A) {
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      A.re[i][j] = p[i * M + j];
-      A.im[i][j] = i == j ? 0.0 : p[j * M + i];
-    }
-  herm::mirror_lower(A);
-}
-
 // spatial, second half: one thread per (f, k).  A, C summed over the slices in order; B = H C H; H A H = B solved in
-// closed form (A exactly 0 -> H = 0; a failed Cholesky of A sets the singular status); + eps I; / trace.
+// closed form (A exactly 0 -> H = 0; a failed Cholesky of A sets the singular status); + eps I; / trace.  The body up to
+// "+ eps I" is mn_riccati_kernel's (assx_mnmf.hip) but for the indexing; see there why it is not one function.
 template <int M>
 __global__ void __launch_bounds__(WAVE) cv_riccati_kernel(Cx<double>* __restrict__ H, const double* __restrict__ part,
                                                           int normalize, double eps, int32_t* __restrict__ status,
@@ -405,8 +390,8 @@ __global__ void __launch_bounds__(WAVE) cv_riccati_kernel(Cx<double>* __restrict
     for (int e = 0; e < MM; ++e) pa[e] += p[e], pc[e] += p[MM + e];
   }
   Mat<M> A, C, Ho, Bm, T1;
-  unpack_herm<M>(pa, A);
-  unpack_herm<M>(pc, C);
+  herm::unpack_herm<M>(pa, A);
+  herm::unpack_herm<M>(pc, C);
   Cx<double>* Hp = H + (size_t)i * MM;
 #pragma unroll
   for (int r = 0; r < M; ++r)

@@ -1,10 +1,13 @@
-// What MultichannelISNMF (assx_mnmf.hip) and FastMultichannelISNMF (assx_fastmnmf.hip) share: the limits and tile
-// sizes, the fixed-order reductions of a workgroup, the slice sum of the activation update, and the dispatch and size
-// check of their entry points.
+// What the seven factorisation families share -- FastMNMF (assx_fastmnmf.hip), MNMF (assx_mnmf.hip), covariance-domain
+// MNMF (assx_covnmf.hip), ComplexEUCNMF (assx_cnmf.hip), EUCNTF (assx_ntf.hip), LDPSDTF (assx_psdtf.hip, through
+// assx_sym_linalg.hpp) and the two IPSDTA models (assx_ipsdta.hip): the limits and tile sizes, the fixed-order
+// reductions of a workgroup, the per-utterance sum of partials, the slice sum of the activation update, the slab and
+// slice counts, the carving of a workspace, and the channel dispatch and size check of the two MNMFs' entry points.
 //
-// Both models promise bit-reproducible, batch-independent results.  The order of every sum made here is part of that
-// promise: a wave's butterfly with offsets 32, 16, .., 1; then the waves of a workgroup in index order; then slices in
-// index order.  No float atomics.
+// Every family promises bit-reproducible, batch-independent results.  The order of every sum made here is part of that
+// promise: a wave's butterfly (offsets 32, 16, .., 1); then the waves of a workgroup in index order; then slices in
+// index order.  No float atomics.  The two block sums differ in their arithmetic (0 + r0 + r1 .. against
+// ((r0 + r1) + r2) + r3) and a family keeps the one it was written with.
 #pragma once
 #include "assx_common.hpp"
 
@@ -17,9 +20,36 @@ constexpr int CH = 16;      // (numerator, denominator) pairs a thread accumulat
 constexpr int FS_ACT = 16;  // f slices of the activation update
 constexpr int BLK = 256;    // threads of the per-bin kernels
 constexpr int ABLK = 64;    // threads (frames) of an activation workgroup
+constexpr int SP_SLICES = 8;  // t slices of the spatial sums of the two MNMFs
 
 inline unsigned nblocks(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
 inline int act_slices(int F) { return F < FS_ACT ? F : FS_ACT; }
+// slabs of at least 8 bins, at most cap of them
+inline int slabs8(int n, int cap) {
+  const int s = (n + 7) / 8;
+  return s > cap ? cap : s;
+}
+// t slices of the spatial sums: whole wave tiles of frames, at most SP_SLICES
+inline int sp_slices(int T) {
+  const int tiles = (T + WAVE - 1) / WAVE;
+  return tiles < SP_SLICES ? tiles : SP_SLICES;
+}
+
+// Offsets of the arrays of a workspace, handed out front to back: take(bytes) returns the current offset and advances
+// to the next multiple of align.  A workspace size is a public number: align is 256 or 1 (packed) as the family had it.
+class Carve {
+ public:
+  explicit Carve(size_t align) : align_(align) {}
+  size_t take(size_t bytes) {
+    const size_t at = off_;
+    off_ = align_up(off_ + bytes, align_);
+    return at;
+  }
+  size_t total() const { return off_; }
+
+ private:
+  size_t align_, off_ = 0;
+};
 
 template <typename R>
 __device__ __forceinline__ R wave_sum_down(R v) {  // fixed butterfly; the total lands in lane 0
@@ -43,6 +73,16 @@ __device__ __forceinline__ R block_sum(R v, R* red) {
   return s;
 }
 
+// The sum of v over a workgroup of four waves, returned to every thread: an xor butterfly, then the waves in index
+// order.  red (four doubles) may still be read by a straggler of the previous call, hence the first barrier.
+__device__ __forceinline__ double block_sum_all(double v, double* red) {
+  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();
+  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // The same for the CH (numerator, denominator) pairs of a chunk: every thread brings its partial sums num[c], den[c];
 // thread c < CH returns the workgroup's totals of pair c in (sn, sd), the others (0, 0).  red is free again after the
 // caller's next barrier.
@@ -58,6 +98,26 @@ __device__ __forceinline__ void block_pair_sums(const R (&num)[CH], const R (&de
   sn = 0, sd = 0;
   if (tid < CH)
     for (int w = 0; w < NW; ++w) sn += red[w][2 * tid], sd += red[w][2 * tid + 1];
+}
+
+// The sum of n values, stride apart, by a workgroup of BLK threads in a fixed order: every thread its own stride of
+// BLK, then the workgroup by block_sum (thread 0 returns the total) or, with ALL, by block_sum_all (every thread does).
+template <bool ALL = false>
+__device__ __forceinline__ double strided_sum(const double* __restrict__ p, int n, size_t stride, double* red) {
+  double v = 0;
+  for (int i = threadIdx.x; i < n; i += BLK) v += p[(size_t)i * stride];
+  if constexpr (ALL) return block_sum_all(v, red);
+  return block_sum<double, BLK / WAVE>(v, red);
+}
+
+// out[b] = the sum of partials[b, 0 .. n_per_b) in that order, one workgroup per b: the last step of a loss (covnmf
+// keeps a kernel of its own)
+template <bool ALL = false>
+__global__ void __launch_bounds__(BLK) batch_sum_kernel(const double* __restrict__ partials, double* __restrict__ out,
+                                                        int n_per_b) {
+  __shared__ double red[BLK / WAVE];
+  const double tot = strided_sum<ALL>(partials + (size_t)blockIdx.x * n_per_b, n_per_b, 1, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
 // Second half of both activation updates: V (B, NP, T) *= sqrt(num / max(den, eps)) with num and den the FS slice
@@ -94,7 +154,9 @@ int dispatch_channels(assx_ctx* ctx, const char* label, int M, Fn&& fn) {
   return fail(ctx, ASSX_E_UNSUPPORTED, "%s: n_channels must be in [2, 8], got %d", label, M);
 }
 
-// the context and the sizes of every entry point; label: the model's name in the messages
+// the context and the sizes of every MNMF and FastMNMF entry point; label: the model's name in the messages.  The other
+// families check in an order of their own, which decides the code and the text when two arguments are wrong at once, so
+// each keeps its check
 inline int check_sizes(assx_ctx* ctx, const char* label, bool f64_only, int B, int M, int N, int F, int T, int K,
                        int dtype) {
   ASSX_REQUIRE_CTX(ctx);

@@ -21,7 +21,7 @@
 // the waves of a workgroup in index order, then slices in index order; no float atomics), and no partition depends on
 // B: two runs give the same bits, a batch gives the bits of its single-utterance calls.
 #include "assx_common.hpp"
-#include "assx_mnmf_common.hpp"
+#include "assx_factor_common.hpp"
 #include "assx_widem.hpp"
 
 using namespace assx;
@@ -40,12 +40,13 @@ FmLayout fm_layout(int B, int M, int N, int F, int T, int K, int dtype) {
   const size_t es = dtype == ASSX_F64 ? 8 : 4;
   const size_t plane = (size_t)B * M * F * T * es;
   const size_t part = (size_t)B * act_slices(F) * 2 * N * K * T * es;
+  Carve c(256);
   FmLayout L;
-  L.xt = 0;
-  L.r2 = align_up(L.xt + plane, 256);
-  L.lpart = align_up(L.r2 + (plane > part ? plane : part), 256);
-  L.dws = align_up(L.lpart + (size_t)2 * B * F * sizeof(double), 256);
-  L.total = align_up(L.dws + assx_workspace_bytes(B, M, F, T, 1, dtype), 256);
+  L.xt = c.take(plane);
+  L.r2 = c.take(plane > part ? plane : part);
+  L.lpart = c.take((size_t)2 * B * F * sizeof(double));
+  L.dws = c.take(assx_workspace_bytes(B, M, F, T, 1, dtype));
+  L.total = c.total();
   return L;
 }
 

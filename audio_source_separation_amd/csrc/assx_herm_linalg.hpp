@@ -1,4 +1,5 @@
-// Small Hermitian linear algebra for MultichannelISNMF (csrc/assx_mnmf.hip), one thread per matrix, float64.
+// Small Hermitian linear algebra for MultichannelISNMF (csrc/assx_mnmf.hip), its covariance-domain form
+// (csrc/assx_covnmf.hip) and IPSDTA (csrc/assx_ipsdta.hip), one thread per matrix, float64.
 //
 // Matrices are M x M complex, held as separate real and imaginary arrays (re[i][j], im[i][j]) with static indices, so
 // they live in VGPRs.  Hermitian inputs are read from their lower triangle only.  Everything here is plain arithmetic
@@ -7,6 +8,7 @@
 //   tri_inverse     L^{-1} of a lower-triangular L
 //   herm_sqrt_psd   (C)^{1/2} of a Hermitian C by cyclic Jacobi rotations, eigenvalues clamped at 0
 //   herm_riccati    the positive-definite solution of H A H = B: the matrix geometric mean L^{-H} (L^H B L)^{1/2} L^{-1}
+//   unpack_herm     a Hermitian matrix from its M^2 packed reals
 #pragma once
 #include <math.h>
 
@@ -252,6 +254,19 @@ __host__ __device__ inline int herm_riccati(Mat<M>& A, Mat<M>& B, Mat<M>& H) {
   matmul_ah(Li, A, H);   // L^{-H} S L^{-1}
   hermitize(H);
   return 0;
+}
+
+// A Hermitian matrix packed into M^2 reals (entry (i, j) holds Re A_ij for i >= j and Im A_ji for i < j), to full storage
+template <int M>
+__host__ __device__ inline void unpack_herm(const double* p, Mat<M>& A) {
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      A.re[i][j] = p[i * M + j];
+      A.im[i][j] = i == j ? 0.0 : p[j * M + i];
+    }
+  mirror_lower(A);
 }
 
 }  // namespace herm

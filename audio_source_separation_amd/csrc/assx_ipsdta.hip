@@ -36,6 +36,7 @@
 // The host drivers are templates on the same flag and read one workspace layout (ip_layout: a field the model does not use
 // has size 0); only the spatial updates, two different algorithms, are two functions.
 #include "assx_common.hpp"
+#include "assx_factor_common.hpp"
 #include "assx_herm_linalg.hpp"
 
 using namespace assx;
@@ -92,18 +93,22 @@ struct IpLayout {
 // size 0
 IpLayout ip_layout(const IpGeo& g, bool td) {
   const size_t c = sizeof(cx), N = g.M, terms = N * g.nblk * g.T * sizeof(double);
+  mf::Carve cv(1);
   IpLayout L;
-  L.ri = 0;
-  L.zz = L.ri + N * g.P * g.T * c;
-  L.part = L.zz + N * g.P * g.T * c;
-  L.q = L.part + N * 2 * g.K * g.P * c;
-  L.qb = L.q + (td ? 0 : N * g.F * g.M * g.M * c);
-  L.lossp = L.qb + (td ? terms : 0);
-  L.pi = L.lossp + terms;
-  L.total = L.pi + (td ? N * g.T * sizeof(double) : 0);
+  L.ri = cv.take(N * g.P * g.T * c);
+  L.zz = cv.take(N * g.P * g.T * c);
+  L.part = cv.take(N * 2 * g.K * g.P * c);
+  L.q = cv.take(td ? 0 : N * g.F * g.M * g.M * c);
+  L.qb = cv.take(td ? terms : 0);
+  L.lossp = cv.take(terms);
+  L.pi = cv.take(td ? N * g.T * sizeof(double) : 0);
+  L.total = cv.total();
   return L;
 }
 
+// Complex arithmetic on double2, not the Cx<double> helpers of assx_common.hpp: with arrays of the aligned struct the
+// sweep, step and loss kernels reserve more scratch than with the native vector type.  cdiv (unscaled) and csqrt_ (half
+// sums) have no counterpart there in any case.
 __device__ __forceinline__ cx cmul(cx a, cx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ cx cmulc(cx a, cx b) {  // a conj(b)
   return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
@@ -432,14 +437,6 @@ __global__ void __launch_bounds__(BLK) ip_act_kernel(const cx* __restrict__ U, d
   H[idx] = H[idx] * sqrt(fmax(num, 0.0) / fmax(den, eps));
 }
 
-__device__ __forceinline__ double ip_block_sum(double v, double* red) {
-  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ void __launch_bounds__(BLK) ip_norm_kernel(cx* __restrict__ U, double* __restrict__ H, IpGeo g) {
   __shared__ double red[NW];
   const size_t nk = blockIdx.x;
@@ -449,7 +446,7 @@ __global__ void __launch_bounds__(BLK) ip_norm_kernel(cx* __restrict__ U, double
     const IpBlock bk = ip_block(g, b);
     for (int i = 0; i < bk.nb; ++i) tr += Uk[bk.off + i * bk.nb + i].x;
   }
-  tr = ip_block_sum(tr, red);
+  tr = mf::block_sum_all(tr, red);
   for (int e = threadIdx.x; e < g.P; e += BLK) Uk[e] = make_double2(Uk[e].x / tr, Uk[e].y / tr);
   for (int t = threadIdx.x; t < g.T; t += BLK) H[nk * g.T + t] = H[nk * g.T + t] * tr;
 }
@@ -689,8 +686,8 @@ __global__ void __launch_bounds__(BLK) ip_loss_kernel(const cx* __restrict__ W, 
   const size_t n_terms = (size_t)g.M * g.nblk * g.T;
   double v = 0.0;
   for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += lossp[e];
-  v = ip_block_sum(v, red);
-  const double ldw = ip_block_sum(ip_logdet_w(W, eps, g), red);
+  v = mf::block_sum_all(v, red);
+  const double ldw = mf::block_sum_all(ip_logdet_w(W, eps, g), red);
   if (threadIdx.x == 0) loss[0] = v - 2.0 * (double)g.T * ldw;
 }
 
@@ -905,7 +902,7 @@ __global__ void __launch_bounds__(BLK) ip_tloss_kernel(const cx* __restrict__ W,
   const size_t n_terms = (size_t)g.M * g.nblk * g.T, T = g.T;
   double v = 0.0;
   for (size_t e = threadIdx.x; e < n_terms; e += BLK) v += ld[e];
-  v = ip_block_sum(v, red);
+  v = mf::block_sum_all(v, red);
   double u = 0.0;
   for (size_t e = threadIdx.x; e < (size_t)g.M * T; e += BLK) {
     const size_t n = e / T, t = e % T;
@@ -913,8 +910,8 @@ __global__ void __launch_bounds__(BLK) ip_tloss_kernel(const cx* __restrict__ W,
     for (int b = 0; b < g.nblk; ++b) s += qb[(n * g.nblk + b) * T + t];
     u += log(1.0 + (2.0 / nu) * s);
   }
-  u = ip_block_sum(u, red);
-  const double ldw = ip_block_sum(ip_logdet_w(W, eps, g), red);
+  u = mf::block_sum_all(u, red);
+  const double ldw = mf::block_sum_all(ip_logdet_w(W, eps, g), red);
   if (threadIdx.x == 0) loss[0] = (v + 0.5 * (nu + 2.0 * (double)g.F) * u) - 2.0 * (double)g.T * ldw;
 }
 

@@ -13,7 +13,7 @@
 //   spatial     mn_spatial_partial_kernel (t slice, f, b): one wave recomputes P, y, lam for 64 frames at a time and
 //               sums lam P and lam y y^H per (f, n) through LDS;  mn_riccati_kernel per (b, f, n): B = H C H, H A H = B
 //               by the closed form of assx_herm_linalg.hpp (H = 0 where A is exactly 0), + eps I, / trace
-//   loss        mn_eval_kernel<LOSS> (per workgroup partials);  mn_loss_finalize_kernel per b
+//   loss        mn_eval_kernel<LOSS> (per workgroup partials);  batch_sum_kernel per b
 //   separate    mn_eval_kernel<SEP>: Y (B,N,F,T) = lam_n (H_n y)[ref]
 //
 // P is never materialised: it is recomputed in registers wherever it is needed.  Every reduction has a fixed order
@@ -23,7 +23,7 @@
 // AGPRs; only the per-(f, n) Riccati kernels use scratch, from M = 6 on (profiles/mnmf_kernel_resource_usage.md).
 #include "assx_common.hpp"
 #include "assx_herm_linalg.hpp"
-#include "assx_mnmf_common.hpp"
+#include "assx_factor_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
@@ -32,13 +32,7 @@ using herm::Mat;
 namespace {
 
 constexpr int EBLK = 128;    // threads (frames) of an evaluation workgroup
-constexpr int SP_SLICES = 8; // t slices of the spatial sums
 constexpr int MODE_AB = 1, MODE_LOSS = 2, MODE_SEP = 3;
-
-inline int sp_slices(int T) {
-  const int tiles = (T + WAVE - 1) / WAVE;
-  return tiles < SP_SLICES ? tiles : SP_SLICES;
-}
 
 struct MnLayout {
   size_t ab, actp, latp, spp, lpart, total;
@@ -48,13 +42,14 @@ struct MnLayout {
 // spp: spatial slice partials (B,F,S,N,2*M*M); lpart: loss partials (B,F,nblocks(T, EBLK)).  All float64.
 MnLayout mn_layout(int B, int M, int N, int F, int T, int K) {
   const size_t d = sizeof(double);
+  Carve c(256);
   MnLayout L;
-  L.ab = 0;
-  L.actp = align_up(L.ab + (size_t)2 * B * N * F * T * d, 256);
-  L.latp = align_up(L.actp + (size_t)B * act_slices(F) * 2 * K * T * d, 256);
-  L.spp = align_up(L.latp + (size_t)B * F * 2 * N * K * d, 256);
-  L.lpart = align_up(L.spp + (size_t)B * F * sp_slices(T) * N * 2 * M * M * d, 256);
-  L.total = align_up(L.lpart + (size_t)B * F * nblocks(T, EBLK) * d, 256);
+  L.ab = c.take((size_t)2 * B * N * F * T * d);
+  L.actp = c.take((size_t)B * act_slices(F) * 2 * K * T * d);
+  L.latp = c.take((size_t)B * F * 2 * N * K * d);
+  L.spp = c.take((size_t)B * F * sp_slices(T) * N * 2 * M * M * d);
+  L.lpart = c.take((size_t)B * F * nblocks(T, EBLK) * d);
+  L.total = c.total();
   return L;
 }
 
@@ -241,17 +236,6 @@ __global__ void __launch_bounds__(EBLK) mn_eval_kernel(const Cx<double>* __restr
     const double s = block_sum<double, EBLK / WAVE>(term, red);
     if (tid == 0) lpart[((size_t)b * F + f) * gridDim.x + blockIdx.x] = s;
   }
-}
-
-// per b: the loss partials summed over (f, t block) in ascending order
-__global__ void __launch_bounds__(BLK) mn_loss_finalize_kernel(const double* __restrict__ lpart, double* __restrict__ loss,
-                                                               int n_per_b) {
-  __shared__ double red[BLK / WAVE];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  double s = 0.0;
-  for (int i = tid; i < n_per_b; i += BLK) s += lpart[(size_t)b * n_per_b + i];
-  s = block_sum<double, BLK / WAVE>(s, red);
-  if (tid == 0) loss[b] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -539,19 +523,9 @@ __global__ void __launch_bounds__(WAVE) mn_spatial_partial_kernel(const Cx<doubl
 }
 
 // spatial, second half: one thread per (b, f, n).  A, C summed over the slices in order; B = H C H; H A H = B solved
-// in closed form (A exactly 0 -> H = 0; a failed Cholesky of A sets the singular status); + eps I; / trace.
-template <int M>
-__device__ __forceinline__ void unpack_herm(const double* p, Mat<M>& A) {
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      A.re[i][j] = p[i * M + j];
-      A.im[i][j] = i == j ? 0.0 : p[j * M + i];
-    }
-  herm::mirror_lower(A);
-}
-
+// in closed form (A exactly 0 -> H = 0; a failed Cholesky of A sets the singular status); + eps I; / trace.  The body up
+// to "+ eps I" is also cv_riccati_kernel's (assx_covnmf.hip), which indexes part and status differently: as one shared
+// device function the M = 8 instance there spills more, so the two stay apart.
 template <int M>
 __global__ void __launch_bounds__(WAVE) mn_riccati_kernel(Cx<double>* __restrict__ H, const double* __restrict__ part,
                                                           int normalize, double eps, int32_t* __restrict__ status,
@@ -570,8 +544,8 @@ __global__ void __launch_bounds__(WAVE) mn_riccati_kernel(Cx<double>* __restrict
     for (int e = 0; e < MM; ++e) pa[e] += p[e], pc[e] += p[MM + e];
   }
   Mat<M> A, C, Ho, Bm, T1;
-  unpack_herm<M>(pa, A);
-  unpack_herm<M>(pc, C);
+  herm::unpack_herm<M>(pa, A);
+  herm::unpack_herm<M>(pc, C);
   Cx<double>* Hp = H + (size_t)i * MM;
 #pragma unroll
   for (int r = 0; r < M; ++r)
@@ -765,8 +739,8 @@ int assx_mnmf_loss(assx_ctx* ctx, const void* X, const void* Tb, const void* V, 
                        (const double*)Tb, (const double*)V, (const double*)Z, (const Cx<double>*)H, eps, nullptr, lpart,
                        nullptr, 0, status, B, N, F, T, K);
     ASSX_LAUNCH_CHECK(ctx, "mn_eval_kernel<loss>");
-    hipLaunchKernelGGL(mn_loss_finalize_kernel, dim3(B), dim3(BLK), 0, st, (const double*)lpart, loss, F * tb);
-    ASSX_LAUNCH_CHECK(ctx, "mn_loss_finalize_kernel");
+    hipLaunchKernelGGL(batch_sum_kernel<false>, dim3(B), dim3(BLK), 0, st, (const double*)lpart, loss, F * tb);
+    ASSX_LAUNCH_CHECK(ctx, "batch_sum_kernel");
     return 0;
   });
 }

@@ -29,7 +29,7 @@
 // its single calls, assx_ntf_iterate those of repeated assx_ntf_update.  Contraction is off for the whole file and every
 // fused multiply-add is written out, so that the loss riding on the basis pass and assx_ntf_loss round alike.
 #include "assx_common.hpp"
-#include "assx_mnmf_common.hpp"
+#include "assx_factor_common.hpp"
 
 #pragma clang fp contract(off)
 
@@ -39,6 +39,7 @@ using mf::CH;
 using mf::KMAX;
 using mf::block_sum;
 using mf::nblocks;
+using mf::strided_sum;
 
 namespace {
 
@@ -46,11 +47,6 @@ constexpr int NW = BLK / WAVE;  // waves of a workgroup
 constexpr int NCMAX = 32;       // channels
 constexpr int NCH = 8;          // channels whose Xh a thread holds at once
 constexpr int IS_MAX = 32;      // bin slabs of the activation pass, at least 8 bins each
-
-inline int nt_slabs(int I) {
-  const int s = (I + 7) / 8;
-  return s > IS_MAX ? IS_MAX : s;
-}
 
 struct NtLayout {
   size_t gv, gt, g, lossp, vnum, vden, zp, total;
@@ -61,15 +57,16 @@ struct NtLayout {
 // (B,N,I,K).  All float64, packed: the size grows with every one of B, N, I, J and K.
 NtLayout nt_layout(int B, int N, int I, int J, int K) {
   const size_t d = sizeof(double), bkk = (size_t)B * K * K * d, bkj = (size_t)B * K * J * d;
+  mf::Carve c(1);
   NtLayout L;
-  L.gv = 0;
-  L.gt = L.gv + bkk;
-  L.g = L.gt + bkk;
-  L.lossp = L.g + bkk;
-  L.vnum = L.lossp + (size_t)B * I * d;
-  L.vden = L.vnum + (size_t)nt_slabs(I) * bkj;
-  L.zp = L.vden + bkj;
-  L.total = L.zp + (size_t)B * N * I * K * d;
+  L.gv = c.take(bkk);
+  L.gt = c.take(bkk);
+  L.g = c.take(bkk);
+  L.lossp = c.take((size_t)B * I * d);
+  L.vnum = c.take((size_t)mf::slabs8(I, IS_MAX) * bkj);
+  L.vden = c.take(bkj);
+  L.zp = c.take((size_t)B * N * I * K * d);
+  L.total = c.total();
   return L;
 }
 
@@ -84,13 +81,6 @@ __device__ __forceinline__ double nt_block_sums(double (&acc)[CH], double (*red)
   if (tid < CH)
     for (int w = 0; w < NW; ++w) s += red[w][tid];
   return s;
-}
-
-// the sum of n values in a fixed order: every thread its stride, then the workgroup; thread 0 returns it
-__device__ __forceinline__ double nt_strided_sum(const double* __restrict__ p, int n, double* red) {
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += BLK) v += p[i];
-  return block_sum<double, NW>(v, red);
 }
 
 // zt (N,K) = Z[n,k] Tb[i,k] of one bin, into LDS
@@ -144,7 +134,7 @@ __global__ void __launch_bounds__(BLK) nt_gram_kernel(const double* __restrict__
   __shared__ double redl[NW];
   if (blockIdx.x >= (unsigned)(B * K)) {
     const size_t b = blockIdx.x - (unsigned)(B * K);
-    const double tot = nt_strided_sum(lossp + b * I, I, redl);
+    const double tot = strided_sum(lossp + b * I, I, 1, redl);
     if (threadIdx.x == 0) loss[b] = tot;
     return;
   }
@@ -341,13 +331,6 @@ __global__ void __launch_bounds__(BLK) nt_loss_kernel(const double* __restrict__
   if (threadIdx.x == 0) lossp[bi] = tot;
 }
 
-__global__ void __launch_bounds__(BLK) nt_loss_sum_kernel(const double* __restrict__ lossp, double* __restrict__ loss,
-                                                          int I) {
-  __shared__ double redl[NW];
-  const double tot = nt_strided_sum(lossp + (size_t)blockIdx.x * I, I, redl);
-  if (threadIdx.x == 0) loss[blockIdx.x] = tot;
-}
-
 __global__ void __launch_bounds__(BLK) nt_recon_kernel(const double* __restrict__ Z, const double* __restrict__ Tb,
                                                        const double* __restrict__ V, double* __restrict__ Xh, int N,
                                                        int I, int J, int K) {
@@ -419,7 +402,7 @@ int nt_update(assx_ctx* ctx, const double* X, double* Z, double* Tb, double* V, 
   ASSX_LAUNCH_CHECK(ctx, "nt_basis_kernel");
   rc = nt_gram(ctx, 1, Z, Tb, V, w, L, loss_prev, d, st);
   if (rc) return rc;
-  const int IS = nt_slabs(I), nchunk = (K + CH - 1) / CH, jtiles = (int)nblocks((size_t)J, WAVE);
+  const int IS = mf::slabs8(I, IS_MAX), nchunk = (K + CH - 1) / CH, jtiles = (int)nblocks((size_t)J, WAVE);
   hipLaunchKernelGGL(nt_act_kernel, dim3((unsigned)(B * jtiles), (unsigned)IS), dim3(WAVE * nchunk), 0, st, X,
                      (const double*)Z, (const double*)Tb, (const double*)V, g, (double*)(w + L.vnum),
                      (double*)(w + L.vden), N, I, J, K, IS, jtiles);
@@ -446,8 +429,8 @@ int nt_loss(assx_ctx* ctx, const double* X, const double* Z, const double* Tb, c
   hipLaunchKernelGGL(nt_loss_kernel, dim3((unsigned)(d.B * d.I)), dim3(BLK), 0, st, X, Z, Tb, V, lossp, d.N, d.I, d.J,
                      d.K);
   ASSX_LAUNCH_CHECK(ctx, "nt_loss_kernel");
-  hipLaunchKernelGGL(nt_loss_sum_kernel, dim3((unsigned)d.B), dim3(BLK), 0, st, (const double*)lossp, loss, d.I);
-  ASSX_LAUNCH_CHECK(ctx, "nt_loss_sum_kernel");
+  hipLaunchKernelGGL(mf::batch_sum_kernel<false>, dim3((unsigned)d.B), dim3(BLK), 0, st, (const double*)lossp, loss, d.I);
+  ASSX_LAUNCH_CHECK(ctx, "batch_sum_kernel");
   return 0;
 }
 

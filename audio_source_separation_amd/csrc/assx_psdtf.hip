@@ -37,7 +37,7 @@ using sl::Scratch;
 namespace {
 
 constexpr int MMAX = sl::NMAX;
-constexpr int KMAX = 64;
+using mf::KMAX;
 constexpr int KC = 8;       // bases of one pass of the contraction
 constexpr int S_MAX = 16;   // frame slabs of the contraction, at least 64 frames each
 
@@ -54,13 +54,14 @@ struct PtLayout {
 // eps) (B,T); lossp: the loss per frame (B,T)
 PtLayout pt_layout(int B, int M, int T, int K) {
   const size_t d = sizeof(double), mm = (size_t)M * M;
+  mf::Carve c(1);
   PtLayout L;
-  L.yinv = 0;
-  L.zz = L.yinv + (size_t)B * T * mm * d;
-  L.part = L.zz + (size_t)B * T * mm * d;
-  L.ldx = L.part + (size_t)B * pt_slabs(T) * 2 * K * mm * d;
-  L.lossp = L.ldx + (size_t)B * T * d;
-  L.total = L.lossp + (size_t)B * T * d;
+  L.yinv = c.take((size_t)B * T * mm * d);
+  L.zz = c.take((size_t)B * T * mm * d);
+  L.part = c.take((size_t)B * pt_slabs(T) * 2 * K * mm * d);
+  L.ldx = c.take((size_t)B * T * d);
+  L.lossp = c.take((size_t)B * T * d);
+  L.total = c.total();
   return L;
 }
 
@@ -235,7 +236,7 @@ __global__ void __launch_bounds__(BLK) pt_norm_kernel(double* V, double* H, int 
 
 // sum_i log max(lambda_i, eps) of the eigenvalues on the diagonal of A
 __device__ __forceinline__ double pt_logdet(const double* A, int M, double eps, Scratch& s) {
-  return sl::block_sum(threadIdx.x < M ? log(fmax(A[threadIdx.x * LD + threadIdx.x], eps)) : 0.0, s);
+  return mf::block_sum_all(threadIdx.x < M ? log(fmax(A[threadIdx.x * LD + threadIdx.x], eps)) : 0.0, s.red);
 }
 
 __global__ void __launch_bounds__(BLK) pt_ldx_kernel(const double* __restrict__ X, double* __restrict__ ldx, int32_t* status,
@@ -267,20 +268,11 @@ __global__ void __launch_bounds__(BLK) pt_loss_kernel(const double* __restrict__
   sl::ata(C, Bm, M);  // Y^-1
   double tr = 0;
   for (int e = threadIdx.x; e < (int)mm; e += BLK) tr += X[bt * mm + e] * Bm[(e % M) * LD + e / M];
-  tr = sl::block_sum(tr, s);
+  tr = mf::block_sum_all(tr, s.red);
   if (!sl::jacobi(A, nullptr, M, s)) st |= sl::ST_NOT_CONVERGED;
   const double ldy = pt_logdet(A, M, eps, s);
   if (threadIdx.x == 0) lossp[bt] = tr - (ldx[bt] - ldy) - M;
   pt_flag(status, b, st);
-}
-
-__global__ void __launch_bounds__(BLK) pt_loss_sum_kernel(const double* __restrict__ lossp, double* __restrict__ loss,
-                                                          int T) {
-  __shared__ Scratch s;
-  double v = 0;
-  for (int t = threadIdx.x; t < T; t += BLK) v += lossp[(size_t)blockIdx.x * T + t];
-  v = sl::block_sum(v, s);
-  if (threadIdx.x == 0) loss[blockIdx.x] = v;
 }
 
 __global__ void __launch_bounds__(BLK) pt_recon_kernel(const double* __restrict__ V, const double* __restrict__ H,
@@ -378,8 +370,8 @@ int pt_loss(assx_ctx* ctx, const double* X, const double* V, const double* H, do
   hipLaunchKernelGGL(pt_loss_kernel, dim3((unsigned)(d.B * d.T)), dim3(BLK), 0, st, X, V, H,
                      (const double*)((char*)ws + L.ldx), lossp, status, eps, d.M, d.T, d.K);
   ASSX_LAUNCH_CHECK(ctx, "pt_loss_kernel");
-  hipLaunchKernelGGL(pt_loss_sum_kernel, dim3((unsigned)d.B), dim3(BLK), 0, st, (const double*)lossp, loss, d.T);
-  ASSX_LAUNCH_CHECK(ctx, "pt_loss_sum_kernel");
+  hipLaunchKernelGGL(mf::batch_sum_kernel<true>, dim3((unsigned)d.B), dim3(BLK), 0, st, (const double*)lossp, loss, d.T);
+  ASSX_LAUNCH_CHECK(ctx, "batch_sum_kernel");
   return 0;
 }
 

@@ -25,6 +25,7 @@
 // routine depends on its input alone.
 #pragma once
 #include "assx_common.hpp"
+#include "assx_factor_common.hpp"
 
 namespace assx {
 namespace sl {
@@ -45,15 +46,6 @@ struct Scratch {
   double bc[2];
   int flag;
 };
-
-// the workgroup's sum, returned to every thread
-__device__ __forceinline__ double block_sum(double v, Scratch& s) {
-  for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & (WAVE - 1)) == 0) s.red[threadIdx.x / WAVE] = v;
-  __syncthreads();
-  return ((s.red[0] + s.red[1]) + s.red[2]) + s.red[3];
-}
 
 __device__ __forceinline__ void copy(const double* A, double* W, int n) {
   for (int e = threadIdx.x; e < n * n; e += BLK) W[(e / n) * LD + e % n] = A[(e / n) * LD + e % n];
@@ -202,8 +194,8 @@ __device__ __forceinline__ bool jacobi(double* A, double* Vv, int n, Scratch& s)
       else if (i == j)
         dg += v * v;
     }
-    off = block_sum(off, s);
-    dg = block_sum(dg, s);
+    off = mf::block_sum_all(off, s.red);
+    dg = mf::block_sum_all(dg, s.red);
     conv = off <= 1e-32 * (dg + 2.0 * off);
     if (conv || off != off || sweep == SWEEPS) break;
     for (int r = 0; r < m - 1; ++r) {
