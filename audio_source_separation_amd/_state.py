@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._device import to_device, to_numpy, torch
+from ._loss import LazyLossList
 
 
 class _Entry:
@@ -160,7 +161,7 @@ class DeviceArray:
             raise AttributeError("'%s' object has no attribute '%s'" % (type(obj).__name__, self.attr))
         if ent.host is None:
             a = to_numpy(ent.dev, np.complex128 if self.complex_ else np.float64)
-            a = a if obj._batched else a[0]
+            a = obj._unbatch(a)
             # in the reference these are plain attributes: `model.demix_filter[...] *= s` takes effect at the next
             # update.  The snapshot is tracked: a write drops the device copy, the next kernel uploads the host array.
             a = a.view(TrackedArray)
@@ -195,18 +196,96 @@ class DeviceState:
             self._engine = Engine(dtype=self.dtype, device=self.device)
         return self._engine
 
-    def _steps_are(self, owner, names):
-        """True while every method in `names` is still `owner`'s own.  The loop goes to the one-call `*_iterate` entry only
-        then: a subclass that overrides a step keeps the Python loop, which runs what it made of it."""
+    # ---- the loop rule ------------------------------------------------------------------------
+    _OWN_STEPS = ()  # a model's methods whose override sends the loop back to the Python loop
+
+    def _fast_loop_ok(self):
+        """The ONE statement of the rule: the loop goes to the library's one-call `*_iterate` entry only while nothing
+        observes the model between iterations -- no callbacks, every step still the model's own (a subclass that
+        overrides one keeps the Python loop, which runs what it made of it), and any loss that is recorded goes to the
+        list that can hold it on the device.  The model is the first class of the MRO that declares `_OWN_STEPS`; a model
+        with further conditions overrides this and calls super() first."""
+        if getattr(self, "callbacks", None) is not None:
+            return False
         cls = type(self)
-        return all(getattr(cls, n) is getattr(owner, n) for n in names)
+        owner = next(c for c in cls.__mro__ if "_OWN_STEPS" in vars(c))
+        if not all(getattr(cls, n) is getattr(owner, n) for n in owner._OWN_STEPS):
+            return False
+        return not getattr(self, "recordable_loss", True) or isinstance(self.loss, LazyLossList)
+
+    def _iterate_block(self, n_entries, touched, call, B=None):
+        """One `*_iterate` call: `call(loss)` with the (n_entries, B) float64 block its losses go to (None when they are
+        not recorded; a model without `recordable_loss` always records), then the arrays it wrote are `touched` and the
+        block joins `loss` without a host sync.  B: the utterances of `_X` unless given.  Returns the block."""
+        loss = None
+        if getattr(self, "recordable_loss", True):
+            loss = self._engine.empty((n_entries, int(self._X.shape[0]) if B is None else B), dtype=torch.float64)
+        call(loss)
+        self._touch(*touched)
+        if loss is not None:
+            self.loss.append_device_block(loss, self._batched)
+        return loss
+
+    # ---- the front of _reset: refusals before a device is touched, then upload and draws ---------------------------
+    def _require_float64(self, dtype, complex_ok=False):
+        if str(dtype) not in ('float64', 'double') + (('complex128',) if complex_ok else ()):
+            raise ValueError("{} supports float64 only, got dtype={!r}".format(
+                getattr(self, "_LABEL", None) or type(self).__name__, dtype))
+
+    def _require_n_basis(self):
+        n_basis = self.n_basis
+        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
+            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        return n_basis
+
+    @staticmethod
+    def _shape_of(x):
+        """the shape of an ndarray, a tensor or a nested sequence, as a tuple of ints"""
+        return tuple(int(s) for s in x.shape) if hasattr(x, "shape") else np.shape(x)
+
+    def _upload(self, x, dtype):
+        """`x` as a contiguous device tensor with the utterance axis in front (added unless the model is batched)."""
+        Xd = to_device(x, dtype, self._engine.dev)
+        if not self._batched:
+            Xd = Xd.unsqueeze(0)
+        return Xd.contiguous()
+
+    def _check_warm_start_array(self, attr, want, real=True):
+        """Refuses a warm-start array that does not fit the target; returns it, or None while the attribute is absent."""
+        if not hasattr(self, attr):
+            return None
+        a = getattr(self, attr)
+        if real and np.iscomplexobj(a):
+            raise ValueError("{} supports a real {} only".format(type(self).__name__, attr))
+        if tuple(a.shape) != want:
+            raise ValueError("{} has shape {}, the target needs {}".format(attr, tuple(a.shape), want))
+        return a
+
+    def _keep_or_draw(self, attr, draw, dtype=None):
+        """Warm start through `hasattr`, as in the reference: `draw()` runs only while the attribute is absent (the draws
+        come from the global RNG, so their number and order are part of the interface); dtype: an existing value is
+        replaced by a copy of that type."""
+        if not hasattr(self, attr):
+            setattr(self, attr, draw())
+        elif dtype is not None:
+            setattr(self, attr, np.array(getattr(self, attr), dtype=dtype))
+
+    def _unbatch(self, a):
+        """a value with the utterance axis in front, as the caller sees it: without it unless the target had one"""
+        return a if self._batched else a[0]
+
+    # ---- status ------------------------------------------------------------------------------------------------------
+    _SINGULAR_TEXT = "Singular matrix"
+    _STATUS_RAISES = _lib.STATUS_SINGULAR  # other flags are informational (STATUS_COND_REJECT) and stay set
 
     def _check_status(self):
         """Turn device-side flags into the exceptions NumPy would have raised (one sync)."""
-        flags = int(self._status.max().item())
-        if flags & _lib.STATUS_SINGULAR:
+        flags = int(self._status.max().item()) & self._STATUS_RAISES
+        if flags:
             self._status.zero_()
-            raise np.linalg.LinAlgError("Singular matrix")
+            if flags & _lib.STATUS_SINGULAR:
+                raise np.linalg.LinAlgError(self._SINGULAR_TEXT)
+            raise np.linalg.LinAlgError("Eigenvalues did not converge")
 
     def _has(self, name):
         return name in self.__dict__.get("_arrays", {})

@@ -72,14 +72,11 @@ class NMFbase(DeviceState):
 
         n_basis = self.n_basis
         target = self.target
-        ndim = target.dim() if isinstance(target, torch.Tensor) else np.ndim(target)
+        ndim = len(self._shape_of(target))
         if ndim not in (2, 3):
             raise ValueError("target must be (n_bins, n_frames), got {} dims".format(ndim))
         self._batched = ndim == 3
-        Xd = to_device(target, eng.prec.real, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(target, eng.prec.real)
         B, n_bins, n_frames = (int(s) for s in self._X.shape)
 
         # NMF never warm-starts: fresh draws from the global RNG, basis first (nmf.py:36-43)
@@ -95,12 +92,7 @@ class NMFbase(DeviceState):
     def _kind_param(self):
         return 0.0
 
-    def _fast_loop_ok(self):
-        """The loop of update() as ONE library call (assx_nmf_iterate): the steps are this module's own (a subclass
-        overriding update_once keeps the Python loop) and `loss` is still the list the constructor made."""
-        fn = getattr(type(self).update_once, "__func__", type(self).update_once)
-        return getattr(fn, "__module__", None) == __name__ and type(self).update is NMFbase.update \
-            and isinstance(self.loss, LazyLossList)
+    _OWN_STEPS = ("update", "update_once", "_record_loss")
 
     def _record_loss(self):
         loss = self._engine.nmf_loss(self._kind_code(), self._X, self._dev("T", False), self._dev("V", False),
@@ -108,19 +100,16 @@ class NMFbase(DeviceState):
         append_loss(self.loss, loss, self._batched)
 
     def update(self, iteration=100):
-        if iteration > 1 and self._fast_loop_ok():
+        if iteration > 1 and self._fast_loop_ok():  # the rule: DeviceState._fast_loop_ok
             # the first update through update_once(): it validates `algorithm` / `domain` and raises exactly what the
             # reference raises; the remaining ones are enqueued by the library (same entry points, same order)
             self.update_once()
             if self.recordable_loss:
                 self._record_loss()
-            eng, n = self._engine, iteration - 1
-            loss = eng.empty((n, int(self._X.shape[0])), dtype=torch.float64) if self.recordable_loss else None
-            eng.nmf_iterate(n, self._kind_code(), self._X, self._dev("T", False), self._dev("V", False),
-                            domain=self.domain, eps=self.eps, param=self._kind_param(), loss=loss)
-            self._touch("T", "V")
-            if loss is not None:
-                self.loss.append_device_block(loss, self._batched)
+            n = iteration - 1
+            self._iterate_block(n, ("T", "V"), lambda loss: self._engine.nmf_iterate(
+                n, self._kind_code(), self._X, self._dev("T", False), self._dev("V", False), domain=self.domain,
+                eps=self.eps, param=self._kind_param(), loss=loss))
             return
 
         for idx in range(iteration):
@@ -161,6 +150,8 @@ class EUCNMF(NMFbase):
     def update_once_mm(self):
         NMFbase.update_once(self)
 
+    _OWN_STEPS = NMFbase._OWN_STEPS + ("update_once_mm",)
+
 
 class KLNMF(NMFbase):
     """reference: nmf.py:209-266"""
@@ -187,6 +178,8 @@ class KLNMF(NMFbase):
 
     def update_once_mm(self):
         NMFbase.update_once(self)
+
+    _OWN_STEPS = NMFbase._OWN_STEPS + ("update_once_mm",)
 
 
 class ISNMF(NMFbase):
@@ -224,6 +217,8 @@ class ISNMF(NMFbase):
         assert self.domain == 2, "Only domain = 2 is supported."
         NMFbase.update_once(self)
 
+    _OWN_STEPS = NMFbase._OWN_STEPS + ("update_once_mm", "update_once_me")
+
 
 class tNMF(NMFbase):
     """reference: nmf.py:358-429 (Student's t NMF, MM update; domain 2 only)"""
@@ -256,6 +251,8 @@ class tNMF(NMFbase):
     def update_once_mm(self):
         assert self.domain == 2, "`domain` is expected 2."
         NMFbase.update_once(self)
+
+    _OWN_STEPS = NMFbase._OWN_STEPS + ("update_once_mm",)
 
 
 class CauchyNMF(NMFbase):
@@ -295,6 +292,8 @@ class CauchyNMF(NMFbase):
 
     update_once_naive = update_once_mm = update_once_me = update_once_mm_fast = _update_once_checked
 
+    _OWN_STEPS = NMFbase._OWN_STEPS + ("update_once_naive", "update_once_mm", "update_once_me", "update_once_mm_fast")
+
 
 class ComplexNMFbase(DeviceState):
     """reference: nmf.py:58-114.  `phase` holds the angles (n_bins, n_basis, n_frames), as in the reference."""
@@ -310,8 +309,7 @@ class ComplexNMFbase(DeviceState):
             n_basis: number of basis
             recordable_loss: extension: False skips the criterion, `loss` then stays empty.
         """
-        if str(dtype) not in ('float64', 'double', 'complex128'):
-            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+        self._require_float64(dtype, complex_ok=True)
 
         self.n_basis = n_basis
         self.regularizer = regularizer
@@ -342,20 +340,15 @@ class ComplexNMFbase(DeviceState):
         for key in kwargs.keys():
             setattr(self, key, kwargs[key])
 
-        n_basis = self.n_basis
-        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
-            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        n_basis = self._require_n_basis()
         target = self.target
-        ndim = target.dim() if isinstance(target, torch.Tensor) else np.ndim(target)
+        ndim = len(self._shape_of(target))
         if ndim not in (2, 3):
             raise ValueError("target must be (n_bins, n_frames), got {} dims".format(ndim))
 
         eng = self._ensure_engine()
         self._batched = ndim == 3
-        Xd = to_device(target, eng.prec.cplx, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(target, eng.prec.cplx)
         B, n_bins, n_frames = (int(s) for s in self._X.shape)
         self._ws = eng.cnmf_workspace(B, n_bins, n_frames, n_basis)
 
@@ -384,8 +377,7 @@ class ComplexNMFbase(DeviceState):
     def reconstruct(self):
         """Extension: sum_k basis * activation * exp(1j * phase), (n_bins, n_frames) complex -- what the reference's
         users form next (egs/nmf-example/cnmf)."""
-        Y = to_numpy(self._engine.cnmf_reconstruct(*self._model()), np.complex128)
-        return Y if self._batched else Y[0]
+        return self._unbatch(to_numpy(self._engine.cnmf_reconstruct(*self._model()), np.complex128))
 
     def update(self, iteration=100):
         for idx in range(iteration):
@@ -421,16 +413,13 @@ class ComplexEUCNMF(ComplexNMFbase):
 
     @property
     def Beta(self):
-        B = to_numpy(self._engine.cnmf_beta(self._dev("T", False), self._dev("V", False), eps=self.eps), np.float64)
-        return B if self._batched else B[0]
+        return self._unbatch(to_numpy(self._engine.cnmf_beta(self._dev("T", False), self._dev("V", False), eps=self.eps),
+                                      np.float64))
 
     def update_beta(self):
         """nmf.py:669-676.  Nothing to do: Beta is a function of basis and activation, formed where it is used."""
 
-    def _fast_loop_ok(self):
-        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_cnmf_iterate when every step is this module's."""
-        return self._steps_are(ComplexEUCNMF, ("update", "update_once", "update_beta", "_record_loss")) \
-            and isinstance(self.loss, LazyLossList)
+    _OWN_STEPS = ("update", "update_once", "update_beta", "_record_loss")
 
     def _record_loss(self):
         T, V, Phi = self._model()
@@ -438,15 +427,10 @@ class ComplexEUCNMF(ComplexNMFbase):
         append_loss(self.loss, loss, self._batched)
 
     def update(self, iteration=100):
-        if iteration > 0 and self._fast_loop_ok():
-            eng = self._engine
-            loss = eng.empty((iteration, int(self._X.shape[0])), dtype=torch.float64) if self.recordable_loss else None
-            T, V, Phi = self._model()
-            eng.cnmf_iterate(iteration, self._X, T, V, Phi, self._ws, regularizer=self.regularizer, p=self.p,
-                             eps=self.eps, loss=loss)
-            self._touch("T", "V", "Phi")
-            if loss is not None:
-                self.loss.append_device_block(loss, self._batched)
+        if iteration > 0 and self._fast_loop_ok():  # the rule: DeviceState._fast_loop_ok; the loop is assx_cnmf_iterate
+            self._iterate_block(iteration, ("T", "V", "Phi"), lambda loss: self._engine.cnmf_iterate(
+                iteration, self._X, *self._model(), self._ws, regularizer=self.regularizer, p=self.p, eps=self.eps,
+                loss=loss))
             return
 
         super().update(iteration=iteration)
@@ -470,8 +454,7 @@ class MultichannelNMFbase(DeviceState):
         Args:
             n_basis: number of basis
         """
-        if str(dtype) not in ('float64', 'double', 'complex128'):
-            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+        self._require_float64(dtype, complex_ok=True)
 
         self.n_basis = n_basis
         self.loss = LazyLossList()
@@ -555,13 +538,11 @@ class MultichannelISNMF(MultichannelNMFbase):
 
         target = self.target
         name = type(self).__name__
-        n_basis = self.n_basis
-        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
-            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        n_basis = self._require_n_basis()
         is_tensor = isinstance(target, torch.Tensor)
         if not (target.is_complex() if is_tensor else np.iscomplexobj(target)):
             raise ValueError("{} supports complex targets only".format(name))
-        shape = tuple(int(s) for s in target.shape) if hasattr(target, "shape") else np.shape(target)
+        shape = self._shape_of(target)
         if len(shape) != 4:
             raise ValueError("target must be (n_bins, n_frames, n_channels, n_channels), got {} dims".format(len(shape)))
         n_bins, n_frames, n_channels, _n_channels = shape
@@ -572,14 +553,9 @@ class MultichannelISNMF(MultichannelNMFbase):
                                                                              n_channels))
         if n_bins < 1 or n_frames < 1:
             raise ValueError("target must not be empty, got shape {}".format(shape))
-        for attr, want in (("spatial", (n_bins, n_basis, n_channels, n_channels)), ("basis", (n_bins, n_basis)),
-                           ("activation", (n_basis, n_frames))):
-            if hasattr(self, attr):
-                a = getattr(self, attr)
-                if attr != "spatial" and np.iscomplexobj(a):
-                    raise ValueError("{} supports a real {} only".format(name, attr))
-                if tuple(a.shape) != want:
-                    raise ValueError("{} has shape {}, the target needs {}".format(attr, tuple(a.shape), want))
+        self._check_warm_start_array("spatial", (n_bins, n_basis, n_channels, n_channels), real=False)
+        self._check_warm_start_array("basis", (n_bins, n_basis))
+        self._check_warm_start_array("activation", (n_basis, n_frames))
 
         self.n_bins, self.n_frames = n_bins, n_frames
         self.n_channels = n_channels
@@ -590,30 +566,18 @@ class MultichannelISNMF(MultichannelNMFbase):
         self._ws = eng.covnmf_workspace(n_channels, n_bins, n_frames, n_basis)
         self._status = eng.new_status(1)
 
-        if not hasattr(self, 'spatial'):
-            H = np.eye(n_channels, dtype=np.complex128)
-            self.spatial = np.tile(H, reps=(n_bins, n_basis, 1, 1))
-        else:
-            self.spatial = np.array(self.spatial, dtype=np.complex128)
-        if not hasattr(self, 'basis'):
-            self.basis = np.random.rand(n_bins, n_basis)
-        else:
-            self.basis = np.array(self.basis, dtype=np.float64)
-        if not hasattr(self, 'activation'):
-            self.activation = np.random.rand(n_basis, n_frames)
-        else:
-            self.activation = np.array(self.activation, dtype=np.float64)
+        # identity spatial matrices, then basis before activation from the global RNG (nmf.py:714-726)
+        self._keep_or_draw('spatial', lambda: np.tile(np.eye(n_channels, dtype=np.complex128),
+                                                      reps=(n_bins, n_basis, 1, 1)), np.complex128)
+        self._keep_or_draw('basis', lambda: np.random.rand(n_bins, n_basis), np.float64)
+        self._keep_or_draw('activation', lambda: np.random.rand(n_basis, n_frames), np.float64)
 
     def _model(self):
         """(T (F,K), V (K,T), H (F,K,M,M)) on the device: the tensors of the attributes without their leading axis."""
         return self._dev("T", False)[0], self._dev("V", False)[0], self._dev("H", True)[0]
 
-    _STEPS = ("update", "update_once", "update_basis", "update_activation", "update_spatial", "reconstruct",
-              "_record_loss")
-
-    def _fast_loop_ok(self):
-        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_covnmf_iterate when every step is this module's."""
-        return self._steps_are(MultichannelISNMF, self._STEPS) and isinstance(self.loss, LazyLossList)
+    _OWN_STEPS = ("update", "update_once", "update_basis", "update_activation", "update_spatial", "reconstruct",
+                  "_record_loss")
 
     def _record_loss(self):
         T, V, H = self._model()
@@ -622,15 +586,11 @@ class MultichannelISNMF(MultichannelNMFbase):
 
     def update(self, target=None, iteration=100):
         """nmf.py:730-736; `target` is accepted as there and, as there, the model's own target is what is used."""
-        if self._fast_loop_ok():
+        if self._fast_loop_ok():  # the rule: DeviceState._fast_loop_ok; the loop is assx_covnmf_iterate
             if iteration > 0:
-                eng = self._engine
-                loss = eng.empty((iteration, 1), dtype=torch.float64)
-                T, V, H = self._model()
-                eng.covnmf_iterate(iteration, self._X, T, V, H, self._ws, normalize=self.normalize, eps=self.eps,
-                                   loss=loss, status=self._status)
-                self._touch("T", "V", "H")
-                self.loss.append_device_block(loss, False)
+                self._iterate_block(iteration, ("T", "V", "H"), lambda loss: self._engine.covnmf_iterate(
+                    iteration, self._X, *self._model(), self._ws, normalize=self.normalize, eps=self.eps, loss=loss,
+                    status=self._status), B=1)
         else:
             for idx in range(iteration):
                 self.update_once()

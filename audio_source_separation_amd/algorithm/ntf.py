@@ -8,7 +8,7 @@ the loop of `update()` is one call of assx_ntf_iterate.  There is no CPU fallbac
 """
 import numpy as np
 
-from .._device import to_device, to_numpy, torch
+from .._device import to_numpy
 from .._state import DeviceArray, DeviceState
 from .._loss import LazyLossList
 
@@ -32,8 +32,7 @@ class NTFbase(DeviceState):
             n_basis: number of basis
             recordable_loss: extension: False skips the criterion, `loss` then stays empty.
         """
-        if str(dtype) not in ('float64', 'double'):
-            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+        self._require_float64(dtype)
 
         self.n_basis = n_basis
         self.loss = LazyLossList()
@@ -53,10 +52,8 @@ class NTFbase(DeviceState):
 
     def _reset(self, target):
         """Everything of ntf.py:27-35 before the loop: the refusals first, then the device, then the three draws."""
-        n_basis = self.n_basis
-        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
-            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
-        shape = tuple(int(s) for s in target.shape) if hasattr(target, "shape") else np.shape(target)
+        n_basis = self._require_n_basis()
+        shape = self._shape_of(target)
         if len(shape) not in (3, 4):
             raise ValueError("target must be (n_channels, n_bins, n_frames), got {} dims".format(len(shape)))
         n_channels, n_bins, n_frames = shape[-3:]
@@ -69,10 +66,7 @@ class NTFbase(DeviceState):
 
         eng = self._ensure_engine()
         self._batched = len(shape) == 4
-        Xd = to_device(target, eng.prec.real, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(target, eng.prec.real)
         B = int(self._X.shape[0])
         self._ws = eng.ntf_workspace(B, n_channels, n_bins, n_frames, n_basis)
 
@@ -112,23 +106,16 @@ class EUCNTF(NTFbase):
     def _model(self):
         return self._dev("Z", False), self._dev("T", False), self._dev("V", False)
 
-    def _fast_loop_ok(self):
-        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_ntf_iterate when every step is this module's."""
-        return self._steps_are(EUCNTF, ("update", "update_once", "compute_loss")) and isinstance(self.loss, LazyLossList)
+    _OWN_STEPS = ("update", "update_once", "compute_loss")
 
     def update(self, target, iteration=100):
-        if not self._fast_loop_ok():
+        if not self._fast_loop_ok():  # the rule: DeviceState._fast_loop_ok; the loop is assx_ntf_iterate
             return super().update(target, iteration=iteration)
 
         self._reset(target)
         if iteration > 0:
-            eng = self._engine
-            loss = eng.empty((iteration, int(self._X.shape[0])), dtype=torch.float64) if self.recordable_loss else None
-            Z, T, V = self._model()
-            eng.ntf_iterate(iteration, self._X, Z, T, V, self._ws, eps=self.eps, loss=loss)
-            self._touch("Z", "T", "V")
-            if loss is not None:
-                self.loss.append_device_block(loss, self._batched)
+            self._iterate_block(iteration, ("Z", "T", "V"), lambda loss: self._engine.ntf_iterate(
+                iteration, self._X, *self._model(), self._ws, eps=self.eps, loss=loss))
 
     def update_once(self):
         Z, T, V = self._model()
@@ -138,10 +125,8 @@ class EUCNTF(NTFbase):
     def compute_loss(self):
         """sum (X - X_hat)^2: a float64 scalar, or (B,) for a batched target."""
         Z, T, V = self._model()
-        loss = to_numpy(self._engine.ntf_loss(self._X, Z, T, V, self._ws), np.float64)
-        return loss if self._batched else loss[0]
+        return self._unbatch(to_numpy(self._engine.ntf_loss(self._X, Z, T, V, self._ws), np.float64))
 
     def reconstruct(self):
         """Extension: sum_k partitioning * basis * activation, (n_channels, n_bins, n_frames)."""
-        Xh = to_numpy(self._engine.ntf_reconstruct(*self._model()), np.float64)
-        return Xh if self._batched else Xh[0]
+        return self._unbatch(to_numpy(self._engine.ntf_reconstruct(*self._model()), np.float64))

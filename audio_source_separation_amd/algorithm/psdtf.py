@@ -9,7 +9,7 @@ assx_psdtf_*); the loop of `update()` is one call of assx_psdtf_iterate.  There 
 import numpy as np
 
 from .. import _lib
-from .._device import to_device, to_numpy, torch
+from .._device import to_numpy, torch
 from .._state import DeviceArray, DeviceState
 from .._loss import LazyLossList
 
@@ -34,8 +34,7 @@ class PSDTFbase(DeviceState):
             n_basis: number of basis
             recordable_loss: extension: False skips the criterion, `loss` then stays empty.
         """
-        if str(dtype) not in ('float64', 'double'):
-            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+        self._require_float64(dtype)
 
         self.n_basis = n_basis
         self.normalize = normalize
@@ -73,13 +72,11 @@ class PSDTFbase(DeviceState):
 
         target = self.target
         name = type(self).__name__
-        n_basis = self.n_basis
-        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
-            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        n_basis = self._require_n_basis()
         is_tensor = isinstance(target, torch.Tensor)
         if (target.is_complex() if is_tensor else np.iscomplexobj(target)):
             raise ValueError("{} supports real targets only".format(name))
-        shape = tuple(int(s) for s in target.shape) if hasattr(target, "shape") else np.shape(target)
+        shape = self._shape_of(target)
         if len(shape) not in (3, 4):
             raise ValueError("target must be (n_bins, n_bins, n_frames), got {} dims".format(len(shape)))
         n_bins, n_bins2, n_frames = shape[-3:]
@@ -97,40 +94,29 @@ class PSDTFbase(DeviceState):
                              "largest entry)".format(name, self.SYMMETRY_RTOL))
         batched = len(shape) == 4
         lead = (shape[0],) if batched else ()
-        for attr, want in (("basis", lead + (n_bins, n_bins, n_basis)), ("activation", lead + (n_basis, n_frames))):
-            if hasattr(self, attr):
-                a = getattr(self, attr)
-                if np.iscomplexobj(a):
-                    raise ValueError("{} supports a real {} only".format(name, attr))
-                if tuple(a.shape) != want:
-                    raise ValueError("{} has shape {}, the target needs {}".format(attr, tuple(a.shape), want))
-                if attr == "basis" and not np.array_equal(a, np.swapaxes(a, -3, -2)):
-                    raise ValueError("{} supports symmetric bases only".format(name))
+        a = self._check_warm_start_array("basis", lead + (n_bins, n_bins, n_basis))
+        if a is not None and not np.array_equal(a, np.swapaxes(a, -3, -2)):
+            raise ValueError("{} supports symmetric bases only".format(name))
+        self._check_warm_start_array("activation", lead + (n_basis, n_frames))
 
         self.is_complex = False
 
         eng = self._ensure_engine()
         self._batched = batched
-        Xd = to_device(target, eng.prec.real, eng.dev)
-        if not batched:
-            Xd = Xd.unsqueeze(0)
-        Xd = Xd.permute(0, 3, 1, 2)  # (B, T, M, M)
+        Xd = self._upload(target, eng.prec.real).permute(0, 3, 1, 2)  # (B, T, M, M)
         self._X = ((Xd + Xd.transpose(2, 3)) / 2).contiguous()  # exactly symmetric; an exactly symmetric target is unchanged
         B = int(self._X.shape[0])
         self._ws = eng.psdtf_workspace(B, n_bins, n_frames, n_basis)
         self._status = eng.new_status(B)
 
-        if not hasattr(self, 'basis'):
+        def draw_basis():
             V = np.random.rand(*(lead + (n_basis, n_bins)))  # should be positive semi-definite
             V = V[..., :, np.newaxis] * np.eye(n_bins)
-            self.basis = np.ascontiguousarray(np.moveaxis(V, -3, -1))
-        else:
-            self.basis = np.array(self.basis, dtype=np.float64)
+            return np.ascontiguousarray(np.moveaxis(V, -3, -1))
 
-        if not hasattr(self, 'activation'):
-            self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
-        else:
-            self.activation = np.array(self.activation, dtype=np.float64)
+        # basis before activation from the global RNG (psdtf.py:47-59)
+        self._keep_or_draw('basis', draw_basis, np.float64)
+        self._keep_or_draw('activation', lambda: np.random.rand(*(lead + (n_basis, n_frames))), np.float64)
 
         if self.normalize:
             V, H = self._model()
@@ -147,14 +133,9 @@ class PSDTFbase(DeviceState):
             self.__dict__["_arrays"]["V"].dev = p.permute(0, 2, 3, 1)
         return p, self._dev("H", False)
 
-    def _raise_status(self):
-        """Device-side flags become the exception NumPy raises there (one sync)."""
-        flags = int(self._status.max().item())
-        if flags:
-            self._status.zero_()
-            if flags & _lib.STATUS_SINGULAR:
-                raise np.linalg.LinAlgError("Matrix is not positive definite")
-            raise np.linalg.LinAlgError("Eigenvalues did not converge")
+    # what DeviceState._check_status raises here: numpy.linalg.cholesky's text, and the eigen-solves can run out of sweeps
+    _SINGULAR_TEXT = "Matrix is not positive definite"
+    _STATUS_RAISES = _lib.STATUS_SINGULAR | _lib.STATUS_NOT_CONVERGED
 
     def update(self, iteration=100):
         for idx in range(iteration):
@@ -163,7 +144,7 @@ class PSDTFbase(DeviceState):
             if self.recordable_loss:
                 loss = self.compute_loss()
                 self.loss.append(loss if self._batched else loss.sum())
-        self._raise_status()
+        self._check_status()
 
     def update_once(self):
         raise NotImplementedError("Implement `update_once` method.")
@@ -187,26 +168,21 @@ class LDPSDTF(PSDTFbase):
 
         self.algorithm = algorithm
 
-    _STEPS = ("update", "update_once", "update_once_mm", "update_basis_mm", "update_activation_mm", "compute_loss")
+    _OWN_STEPS = ("update", "update_once", "update_once_mm", "update_basis_mm", "update_activation_mm", "compute_loss")
 
     def _fast_loop_ok(self):
-        """Same rule as NMFbase._fast_loop_ok: the loop goes to assx_psdtf_iterate when every step is this module's."""
-        return self._steps_are(LDPSDTF, self._STEPS) and self.algorithm == 'mm' and isinstance(self.loss, LazyLossList)
+        """DeviceState's rule, and assx_psdtf_iterate is the MM loop."""
+        return super()._fast_loop_ok() and self.algorithm == 'mm'
 
     def update(self, iteration=100):
         if not self._fast_loop_ok():
             return super().update(iteration=iteration)
 
         if iteration > 0:
-            eng = self._engine
-            loss = eng.empty((iteration, int(self._X.shape[0])), dtype=torch.float64) if self.recordable_loss else None
-            V, H = self._model()
-            eng.psdtf_iterate(iteration, self._X, V, H, self._ws, eps=self.eps, normalize=self.normalize, loss=loss,
-                              status=self._status)
-            self._touch("V", "H")
-            if loss is not None:
-                self.loss.append_device_block(loss, self._batched)
-        self._raise_status()
+            self._iterate_block(iteration, ("V", "H"), lambda loss: self._engine.psdtf_iterate(
+                iteration, self._X, *self._model(), self._ws, eps=self.eps, normalize=self.normalize, loss=loss,
+                status=self._status))
+        self._check_status()
 
     def update_once(self):
         if self.algorithm == 'mm':
@@ -240,11 +216,11 @@ class LDPSDTF(PSDTFbase):
         for a batched target."""
         V, H = self._model()
         loss = to_numpy(self._engine.psdtf_loss(self._X, V, H, self._ws, eps=self.eps, status=self._status), np.float64)
-        self._raise_status()
-        return loss if self._batched else loss[0]
+        self._check_status()
+        return self._unbatch(loss)
 
     def reconstruct(self):
         """Extension: sum_k activation * basis, (n_bins, n_bins, n_frames), without to_PSD."""
         Xh = to_numpy(self._engine.psdtf_reconstruct(*self._model()).permute(0, 2, 3, 1), np.float64)
-        self._raise_status()
-        return Xh if self._batched else Xh[0]
+        self._check_status()
+        return self._unbatch(Xh)

@@ -76,15 +76,11 @@ class ILRMAbase(DeviceState):
 
     def _upload_input(self):
         eng = self._ensure_engine()
-        X = self.input
-        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
+        ndim = len(self._shape_of(self.input))
         if ndim not in (3, 4):
             raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
         self._batched = ndim == 4
-        Xd = to_device(X, eng.prec.cplx, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(self.input, eng.prec.cplx)
         self._status = eng.new_status(self._X.shape[0])
 
     def _reset(self, **kwargs):
@@ -122,10 +118,8 @@ class ILRMAbase(DeviceState):
         else:
             shape_T, shape_V = lead + (n_sources, n_bins, n_basis), lead + (n_sources, n_basis, n_frames)
         # global NumPy RNG, basis first then activation, exactly as ilrma.py:97-104
-        if not hasattr(self, 'basis'):
-            self.basis = np.random.rand(*shape_T)
-        if not hasattr(self, 'activation'):
-            self.activation = np.random.rand(*shape_V)
+        self._keep_or_draw('basis', lambda: np.random.rand(*shape_T))
+        self._keep_or_draw('activation', lambda: np.random.rand(*shape_V))
 
         self._estimation = None  # = separate(X, W), formed on demand
 
@@ -168,8 +162,7 @@ class ILRMAbase(DeviceState):
             if getattr(self, "_X", None) is None:
                 raise AttributeError("'{}' object has no attribute 'estimation'".format(type(self).__name__))
             Y = self._engine.demix(self._X, self._dev("W", True))
-            Y = to_numpy(Y, np.complex128)
-            self._estimation = Y if self._batched else Y[0]
+            self._estimation = self._unbatch(to_numpy(Y, np.complex128))
         return self._estimation
 
     @estimation.setter
@@ -319,11 +312,7 @@ class GaussILRMA(ILRMAbase):
         Y = eng.demix(self._X, self._Wd, scale=scale)
         self._check_status()
 
-        if isinstance(input, torch.Tensor):
-            output = Y if self._batched else Y[0]
-        else:
-            output = to_numpy(Y, np.complex128)
-            output = output if self._batched else output[0]
+        output = self._unbatch(Y if isinstance(input, torch.Tensor) else to_numpy(Y, np.complex128))
         self.estimation = output
 
         return output
@@ -332,14 +321,9 @@ class GaussILRMA(ILRMAbase):
     _OWN_STEPS = ("update_once", "update_source_model", "update_spatial_model", "_record_loss", "_select_update_pair")
 
     def _fast_loop_plan(self):
-        """dict(normalize=, pb_exponent=) when assx_ilrma_iterate can stand in for the Python loop, else None: nothing
-        observes the model between iterations (no callbacks), the steps are this class's own (a subclass that
-        overrides one keeps the loop), no partitioning function, and a normalisation the entry point knows."""
-        if self.callbacks is not None or self.partitioning:
-            return None
-        if not self._steps_are(GaussILRMA, self._OWN_STEPS):
-            return None
-        if self.recordable_loss and not isinstance(self.loss, LazyLossList):
+        """dict(normalize=, pb_exponent=) when assx_ilrma_iterate can stand in for the Python loop, else None:
+        DeviceState's rule, no partitioning function, and a normalisation the entry point knows."""
+        if not self._fast_loop_ok() or self.partitioning:
             return None
         if not self.normalize:
             return dict(normalize=0, pb_exponent=2.0)
@@ -373,17 +357,13 @@ class GaussILRMA(ILRMAbase):
             C, pbins = self._ensure_plain_covariance()
         elif plan["normalize"] == 2:
             scale = eng.empty((B, N, self.n_bins), complex_=True)
-        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
-        eng.ilrma_iterate(iteration, self._X, self._Wd, self._Td, self._Vd, domain=self.domain, eps=self.eps,
-                          threshold=self.threshold, status=self._status, loss=loss, spatial=spatial, pair=pair,
-                          normalize=plan["normalize"], C=C, power_bins=pbins, scale=scale, ref=self.reference_id,
-                          pb_exponent=plan["pb_exponent"])
+        self._iterate_block(iteration + 1, ("W", "T", "V"), lambda loss: eng.ilrma_iterate(
+            iteration, self._X, self._Wd, self._Td, self._Vd, domain=self.domain, eps=self.eps, threshold=self.threshold,
+            status=self._status, loss=loss, spatial=spatial, pair=pair, normalize=plan["normalize"], C=C,
+            power_bins=pbins, scale=scale, ref=self.reference_id, pb_exponent=plan["pb_exponent"]))
         if spatial == _lib.SPATIAL_IP2:
             self.update_pair = ((pair[0] + iteration - 1) % N, (pair[1] + iteration - 1) % N)
-        self._touch("W", "T", "V")
         self._estimation = None
-        if loss is not None:
-            self.loss.append_device_block(loss, self._batched)
 
     def _reset(self, **kwargs):
         self._resolve_deferred_loss()
@@ -644,11 +624,7 @@ class tILRMA(ILRMAbase):
         Y = eng.demix(self._X, self._Wd, scale=scale)
         self._check_status()
 
-        if isinstance(input, torch.Tensor):
-            output = Y if self._batched else Y[0]
-        else:
-            output = to_numpy(Y, np.complex128)
-            output = output if self._batched else output[0]
+        output = self._unbatch(Y if isinstance(input, torch.Tensor) else to_numpy(Y, np.complex128))
         self.estimation = output
 
         return output

@@ -71,8 +71,7 @@ class IPSDTAbase(DeviceState):
 
     def __init__(self, n_basis=10, normalize=True, callbacks=None, reference_id=0, recordable_loss=True, eps=EPS, *,
                  dtype='float64', device=None):
-        if str(dtype) not in ('float64', 'double'):
-            raise ValueError("{} supports float64 only, got dtype={!r}".format(type(self).__name__, dtype))
+        self._require_float64(dtype)
         if callbacks is not None:
             if callable(callbacks):
                 callbacks = [callbacks]
@@ -184,17 +183,12 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
 
         self._run_callbacks()
 
-        if self.callbacks is None and self._fast_loop_ok():
+        if self._fast_loop_ok():  # the rule: DeviceState._fast_loop_ok; the loop is the model's `iterate` entry point
             if iteration > 0:
-                eng = self._engine
-                loss = eng.empty((iteration,), dtype=torch.float64) if self.recordable_loss else None
-                W, U, H = self._model()
-                self._op("iterate")(iteration, self.spatial_iteration, self._X, W, U, H, self._ws, self.n_blocks,
-                                    eps=self.eps, normalize=self.normalize, loss=loss, status=self._status,
-                                    **self._model_kwargs())
-                self._touch("W", "U", "H")
-                if loss is not None:
-                    self.loss.append_device_block(loss.unsqueeze(1), False)
+                self._iterate_block(iteration, ("W", "U", "H"), lambda loss: self._op("iterate")(
+                    iteration, self.spatial_iteration, self._X, *self._model(), self._ws, self.n_blocks, eps=self.eps,
+                    normalize=self.normalize, loss=None if loss is None else loss.view(-1), status=self._status,
+                    **self._model_kwargs()), B=1)
         else:
             for idx in range(iteration):
                 self.update_once()
@@ -214,15 +208,10 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
 
         return self.estimation
 
-    _STEPS = ("update_once", "update_source_model", "update_source_model_mm", "update_basis_mm", "update_activation_mm",
-              "update_spatial_model", "update_spatial_model_vcd", "normalize_psdtf", "normalize_psdtf_block_diagonal",
-              "compute_negative_loglikelihood", "compute_negative_loglikelihood_block_diagonal")
-
-    def _fast_loop_ok(self):
-        """The loop goes to the model's `iterate` entry point when every step is this module's and `loss` is still the lazy
-        list."""
-        return self._steps_are(_BlockDiagonalIPSDTA, self._STEPS) \
-            and (not self.recordable_loss or isinstance(self.loss, LazyLossList))
+    _OWN_STEPS = ("update_once", "update_source_model", "update_source_model_mm", "update_basis_mm",
+                  "update_activation_mm", "update_spatial_model", "update_spatial_model_vcd", "normalize_psdtf",
+                  "normalize_psdtf_block_diagonal", "compute_negative_loglikelihood",
+                  "compute_negative_loglikelihood_block_diagonal")
 
     def _run_callbacks(self):
         if self.callbacks is not None:
@@ -248,7 +237,7 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
         is_tensor = isinstance(X, torch.Tensor)
         if not (X.is_complex() if is_tensor else np.iscomplexobj(X)):
             raise ValueError("{} needs a complex input (n_channels, n_bins, n_frames)".format(name))
-        shape = tuple(int(s) for s in X.shape)
+        shape = self._shape_of(X)
         if len(shape) != 3:
             raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(len(shape)))
         n_channels, n_bins, n_frames = shape
@@ -258,8 +247,7 @@ class _BlockDiagonalIPSDTA(IPSDTAbase):
                                                                             n_channels))
         if n_bins < 1 or n_frames < 1:
             raise ValueError("input must not be empty, got shape {}".format(shape))
-        if not isinstance(n_basis, (int, np.integer)) or not 1 <= n_basis <= self.N_BASIS_MAX:
-            raise ValueError("n_basis must be an int in [1, {}], got {!r}".format(self.N_BASIS_MAX, n_basis))
+        self._require_n_basis()
         if not isinstance(n_blocks, (int, np.integer)) or not 1 <= n_blocks <= n_bins:
             raise ValueError("n_blocks must be an int in [1, n_bins = {}], got {!r}".format(n_bins, n_blocks))
         if not isinstance(self.spatial_iteration, (int, np.integer)) or self.spatial_iteration < 0:

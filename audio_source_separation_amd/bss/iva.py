@@ -57,15 +57,11 @@ class IVAbase(DeviceState):
             setattr(self, key, kwargs[key])
 
         eng = self._ensure_engine()
-        X = self.input
-        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
+        ndim = len(self._shape_of(self.input))
         if ndim not in (3, 4):
             raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
         self._batched = ndim == 4
-        Xd = to_device(X, eng.prec.cplx, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(self.input, eng.prec.cplx)
         B, n_channels, n_bins, n_frames = (int(s) for s in self._X.shape)
         self._status = eng.new_status(B)
         n_sources = n_channels  # n_channels == n_sources (iva.py:47)
@@ -87,8 +83,7 @@ class IVAbase(DeviceState):
         if self._estimation is None:
             if getattr(self, "_X", None) is None:
                 raise AttributeError("'{}' object has no attribute 'estimation'".format(type(self).__name__))
-            Y = to_numpy(self._engine.demix(self._X, self._Wd), np.complex128)
-            self._estimation = Y if self._batched else Y[0]
+            self._estimation = self._unbatch(to_numpy(self._engine.demix(self._X, self._Wd), np.complex128))
         return self._estimation
 
     @estimation.setter
@@ -232,11 +227,7 @@ class AuxIVAbase(IVAbase):
         Y = eng.demix(self._X, self._Wd, scale=scale)
         self._check_status()
 
-        if isinstance(input, torch.Tensor):
-            output = Y if self._batched else Y[0]
-        else:
-            output = to_numpy(Y, np.complex128)
-            output = output if self._batched else output[0]
+        output = self._unbatch(Y if isinstance(input, torch.Tensor) else to_numpy(Y, np.complex128))
         self.estimation = output
 
         return output
@@ -246,13 +237,9 @@ class AuxIVAbase(IVAbase):
                   "_record_loss", "_refresh_weights", "_select_update_pair")
 
     def _fast_loop_ok(self):
-        if self.callbacks is not None or self._KIND is None:
-            return False
-        if not self._steps_are(AuxIVAbase, self._OWN_STEPS):
-            return False
-        if self.recordable_loss and not isinstance(self.loss, LazyLossList):
-            return False
-        return self.algorithm_spatial in ('IP', 'IP1', 'ISS', 'pairwise', 'IP2')
+        """DeviceState's rule, and what assx_auxiva_iterate knows: a model with kernels, a spatial update on the HIP path."""
+        return super()._fast_loop_ok() and self._KIND is not None \
+            and self.algorithm_spatial in ('IP', 'IP1', 'ISS', 'pairwise', 'IP2')
 
     def _run_fast_loop(self, iteration):
         eng = self._engine
@@ -265,16 +252,14 @@ class AuxIVAbase(IVAbase):
             self._select_update_pair()  # the pair of the first iteration; the library advances it like iva.py:370-382
             spatial, pair = _lib.SPATIAL_IP2, self.update_pair
         r = eng.empty((B, N, T))
-        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
-        eng.auxiva_iterate(iteration, self._KIND, self._X, self._Wd, r, eps=self.eps, threshold=self.threshold,
-                           status=self._status, loss=loss, spatial=spatial, pair=pair)
+        loss = self._iterate_block(iteration + 1, ("W",), lambda loss: eng.auxiva_iterate(
+            iteration, self._KIND, self._X, self._Wd, r, eps=self.eps, threshold=self.threshold, status=self._status,
+            loss=loss, spatial=spatial, pair=pair))
         if spatial == _lib.SPATIAL_IP2:
             self.update_pair = ((pair[0] + iteration - 1) % N, (pair[1] + iteration - 1) % N)
-        self._touch("W")
         self._estimation = None
         if loss is not None:  # r and the last loss entry belong to the final filters
             self._r, self._r_src, self._loss_dev = r, self._Wd, loss[iteration]
-            self.loss.append_device_block(loss, self._batched)
         else:
             self._r = self._loss_dev = None
 

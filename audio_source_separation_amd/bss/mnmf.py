@@ -87,14 +87,13 @@ class MultichannelNMFbase(DeviceState):
         _run_fast_loop(n)       the whole loop as ONE library call
         _loss_dev()             the loss (B,) as a float64 device tensor
         _separate_dev(X)        the sources' images (B, n_sources, n_bins, n_frames) at channel `reference_id`
-        _OWN_STEPS              the methods whose override sends the loop back to the step loop
+        _OWN_STEPS              the methods whose override sends the loop back to the step loop (DeviceState._fast_loop_ok)
     """
     MAX_CHANNELS, MAX_SOURCES, MAX_BASIS = 8, 8, 64
 
     _LABEL = None                  # the model's name in the messages of the limit checks
     _SAMPLES_NOTE = ""             # follows "n_frames < 268435456" in the message of the 2^28 limit
     _CALLBACKS_BEFORE_LOOP = True  # mnmf.py:80-82; FastMNMF's own __call__ (mnmf.py:691-735) has no such call
-    _OWN_STEPS = ()
 
     def __init__(self, n_basis=10, n_sources=None, callbacks=None, reference_id=0, recordable_loss=True, eps=EPS, *,
                  dtype='float64', device=None):
@@ -132,11 +131,10 @@ class MultichannelNMFbase(DeviceState):
         for key in kwargs.keys():
             setattr(self, key, kwargs[key])
 
-        X = self.input
-        ndim = X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)
+        shape = self._shape_of(self.input)
+        ndim = len(shape)
         if ndim not in (3, 4):
             raise ValueError("input must be (n_channels, n_bins, n_frames), got {} dims".format(ndim))
-        shape = tuple(int(d) for d in (X.shape if isinstance(X, torch.Tensor) else np.shape(X)))
         B, n_channels, n_bins, n_frames = (1,) * (4 - ndim) + shape
 
         n_sources = self.n_sources
@@ -165,10 +163,7 @@ class MultichannelNMFbase(DeviceState):
     def _upload_input(self, batched):
         eng = self._ensure_engine()
         self._batched = batched
-        Xd = to_device(self.input, eng.prec.cplx, eng.dev)
-        if not self._batched:
-            Xd = Xd.unsqueeze(0)
-        self._X = Xd.contiguous()
+        self._X = self._upload(self.input, eng.prec.cplx)
 
     def _check_warm_start(self, table, copy=False):
         """table: (device name, attribute name, expected shape with the utterance axis, complex) per array.  The
@@ -240,16 +235,8 @@ class MultichannelNMFbase(DeviceState):
         Y = self._separate_dev(self._X)
         self._set_dev("Y", Y)
         if isinstance(input, torch.Tensor):
-            return Y if self._batched else Y[0]
+            return self._unbatch(Y)
         return self.estimation
-
-    def _fast_loop_ok(self):
-        if self.callbacks is not None:
-            return False
-        owner = next(c for c in type(self).__mro__ if "_OWN_STEPS" in vars(c))  # the model a subclass derives from
-        if not self._steps_are(owner, owner._OWN_STEPS):
-            return False
-        return not self.recordable_loss or isinstance(self.loss, LazyLossList)
 
     def _reset(self, **kwargs):
         raise NotImplementedError("Implement '_reset' method")
@@ -326,19 +313,14 @@ class FastMultichannelISNMF(MultichannelNMFbase):
 
         lead = (B,) if self._batched else ()
         if self.partitioning:
-            if not hasattr(self, 'latent'):
-                self.latent = np.ones(lead + (n_sources, n_basis), dtype=np.float64) / n_sources
-            if not hasattr(self, 'basis'):
-                self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
-            if not hasattr(self, 'activation'):
-                self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
+            self._keep_or_draw('latent', lambda: np.ones(lead + (n_sources, n_basis), dtype=np.float64) / n_sources)
+            self._keep_or_draw('basis', lambda: np.random.rand(*(lead + (n_bins, n_basis))))
+            self._keep_or_draw('activation', lambda: np.random.rand(*(lead + (n_basis, n_frames))))
             table = [("Z", "latent", (B, n_sources, n_basis), False), ("W", "basis", (B, n_bins, n_basis), False),
                      ("H", "activation", (B, n_basis, n_frames), False)]
         else:
-            if not hasattr(self, 'basis'):
-                self.basis = np.random.rand(*(lead + (n_sources, n_bins, n_basis)))
-            if not hasattr(self, 'activation'):
-                self.activation = np.random.rand(*(lead + (n_sources, n_basis, n_frames)))
+            self._keep_or_draw('basis', lambda: np.random.rand(*(lead + (n_sources, n_bins, n_basis))))
+            self._keep_or_draw('activation', lambda: np.random.rand(*(lead + (n_sources, n_basis, n_frames))))
             table = [("W", "basis", (B, n_sources, n_bins, n_basis), False),
                      ("H", "activation", (B, n_sources, n_basis, n_frames), False)]
         self._check_warm_start(table)
@@ -390,21 +372,15 @@ class FastMultichannelISNMF(MultichannelNMFbase):
                   "_record_loss")
 
     def _fast_loop_ok(self):
-        if self.partitioning or self.normalize not in (False, None, 0, '', 'power'):
-            return False
-        return super()._fast_loop_ok()
+        """DeviceState's rule, and what assx_fastmnmf_iterate knows: no partitioning function, 'power' or nothing."""
+        return super()._fast_loop_ok() and not self.partitioning and self.normalize in (False, None, 0, '', 'power')
 
     def _run_fast_loop(self, iteration):
-        eng = self._engine
-        B = int(self._X.shape[0])
-        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
         W, H, g, Q = self._model()
-        eng.fastmnmf_iterate(iteration, self._X, Q, W, H, g, self._ws, normalize=bool(self.normalize), eps=self.eps,
-                             threshold=self.threshold, status=self._status, loss=loss)
-        self._touch("W", "H", "g", "Q")
+        loss = self._iterate_block(iteration + 1, ("W", "H", "g", "Q"), lambda loss: self._engine.fastmnmf_iterate(
+            iteration, self._X, Q, W, H, g, self._ws, normalize=bool(self.normalize), eps=self.eps,
+            threshold=self.threshold, status=self._status, loss=loss))
         self._xt_src = Q if loss is not None else None  # the last projection ran only to record the last loss
-        if loss is not None:
-            self.loss.append_device_block(loss, self._batched)
 
     def __repr__(self):
         s = "FastMNMF("
@@ -512,8 +488,7 @@ class MultichannelISNMF(MultichannelNMFbase):
         if not isinstance(reference_id, (int, np.integer)) or reference_id < 0:
             raise ValueError("reference_id must be a non-negative int, got {!r}".format(reference_id))
 
-        if str(dtype) not in ('float64', 'double', 'complex128'):
-            raise ValueError("MultichannelISNMF supports float64 only, got dtype={!r}".format(dtype))
+        self._require_float64(dtype, complex_ok=True)
 
     def _reset(self, **kwargs):
         """mnmf.py:47-61, 183-240: latent, spatial, basis and activation are drawn (in that order) only when absent."""
@@ -532,12 +507,10 @@ class MultichannelISNMF(MultichannelNMFbase):
             Zsum = Z.sum(axis=-2, keepdims=True)
             Zsum[Zsum < eps] = eps
             self.latent = Z / Zsum
-        if not hasattr(self, 'spatial'):
-            self.spatial = np.tile(np.eye(n_channels, dtype=np.complex128), lead + (n_bins, n_sources, 1, 1))
-        if not hasattr(self, 'basis'):
-            self.basis = np.random.rand(*(lead + (n_bins, n_basis)))
-        if not hasattr(self, 'activation'):
-            self.activation = np.random.rand(*(lead + (n_basis, n_frames)))
+        self._keep_or_draw('spatial', lambda: np.tile(np.eye(n_channels, dtype=np.complex128),
+                                                      lead + (n_bins, n_sources, 1, 1)))
+        self._keep_or_draw('basis', lambda: np.random.rand(*(lead + (n_bins, n_basis))))
+        self._keep_or_draw('activation', lambda: np.random.rand(*(lead + (n_basis, n_frames))))
         # warm-start values are copied (mnmf.py:212-233)
         self._check_warm_start([("Z", "latent", (B, n_sources, n_basis), False),
                                 ("H", "spatial", (B, n_bins, n_sources, n_channels, n_channels), True),
@@ -560,15 +533,9 @@ class MultichannelISNMF(MultichannelNMFbase):
                   "update_latent_sawada", "update_spatial_sawada", "compute_negative_loglikelihood", "_record_loss")
 
     def _run_fast_loop(self, iteration):
-        eng = self._engine
-        B = int(self._X.shape[0])
-        loss = eng.empty((iteration + 1, B), dtype=torch.float64) if self.recordable_loss else None
-        Tb, V, Z, H = self._model()
-        eng.mnmf_iterate(iteration, self._X, Tb, V, Z, H, self._ws, normalize=bool(self.normalize), eps=self.eps,
-                         status=self._status, loss=loss)
-        self._touch("Tb", "V", "Z", "H")
-        if loss is not None:
-            self.loss.append_device_block(loss, self._batched)
+        self._iterate_block(iteration + 1, ("Tb", "V", "Z", "H"), lambda loss: self._engine.mnmf_iterate(
+            iteration, self._X, *self._model(), self._ws, normalize=bool(self.normalize), eps=self.eps,
+            status=self._status, loss=loss))
 
     def __repr__(self):
         s = "IS-MNMF("

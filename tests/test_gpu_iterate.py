@@ -196,3 +196,35 @@ def test_nmf_one_call_loop_keeps_the_reference_errors():
     m = ISNMF(n_basis=2, algorithm="me", domain=1.5)
     with pytest.raises(AssertionError):
         m(np.ones((8, 8)), iteration=3)
+
+
+@pytest.mark.parametrize("cls_name,kw,step", [("EUCNMF", {}, "update_once_mm"), ("ISNMF", dict(algorithm="me"), "update_once_me"),
+                                              ("CauchyNMF", dict(algorithm="mm_fast"), "update_once_mm_fast")])
+def test_nmf_subclass_that_overrides_the_routed_step_sees_every_iteration(cls_name, kw, step):
+    """`update_once` of these classes routes to `update_once_mm` / `_me` / `_mm_fast`: a subclass that overrides the routed
+    step keeps the Python loop (DeviceState._fast_loop_ok), so its override runs in every iteration, not in the first
+    alone, and what it computes is the plain class's result bit for bit."""
+    from audio_source_separation_amd.algorithm import nmf
+    base = getattr(nmf, cls_name)
+    calls = []
+
+    def counted(self):
+        calls.append(step)
+        getattr(super(Counting, self), step)()
+
+    Counting = type("Counting", (base,), {step: counted})
+
+    X = np.random.default_rng(7).random((5, 7)) ** 2 + 1e-3
+    out = []
+    for cls in (base, Counting):
+        np.random.seed(11)
+        m = cls(n_basis=2, **kw)
+        assert m._fast_loop_ok() is (cls is base)
+        Tb, V = m(X, iteration=3)
+        out.append((Tb, V, np.asarray(m.loss)))
+    assert len(calls) == 3
+    a, b = out
+    assert a[2].shape == (3,) and np.all(np.isfinite(a[2]))
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    print("loss, one-call loop:", [float(v).hex() for v in a[2]], "Python loop:", [float(v).hex() for v in b[2]])
+    assert np.array_equal(a[2], b[2])
