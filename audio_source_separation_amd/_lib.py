@@ -22,6 +22,8 @@ NMF_EUC, NMF_KL, NMF_IS_MM, NMF_IS_ME = 0, 1, 2, 3
 NMF_T, NMF_CAUCHY_NAIVE, NMF_CAUCHY_MM, NMF_CAUCHY_ME, NMF_CAUCHY_MM_FAST = 4, 5, 6, 7, 8
 STATUS_SINGULAR, STATUS_COND_REJECT, STATUS_NOT_CONVERGED = 1, 2, 4
 SPATIAL_IP, SPATIAL_ISS, SPATIAL_IP2 = 0, 1, 2
+GRADBSS_IVA, GRADBSS_FDICA = 0, 1
+GRADBSS_FRAME_CHUNK = 1024  # ASSX_GRADBSS_FRAME_CHUNK of include/assx.h: frames of one moment workgroup
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -124,6 +126,11 @@ SIGNATURES = {
     "assx_covnmf_reconstruct": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_covnmf_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_covnmf_iterate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_gradbss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "assx_gradbss_update": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _d, _i, _i, _i, _vp, _vp]),
+    "assx_gradbss_loss": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_gradbss_iterate": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _d, _vp, _i, _i, _i, _vp, _vp]),
+    "assx_fdica_solve_permutation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -1,6 +1,9 @@
 """Blind source separation classes (mirror of the reference's src/bss for the HIP hot path)."""
 
-_EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta", "tIPSDTA": "ipsdta"}
+_EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta", "tIPSDTA": "ipsdta",
+            "GradIVAbase": "iva", "GradLaplaceIVA": "iva", "NaturalGradLaplaceIVA": "iva",
+            "FDICAbase": "fdica", "GradFDICAbase": "fdica", "GradLaplaceFDICA": "fdica",
+            "NaturalGradLaplaceFDICA": "fdica"}
 __all__ = sorted(_EXPORTS)
 
 

@@ -10,6 +10,11 @@ One iteration = two passes over X on the device:
 quadratic forms of the same covariances (Y = W X is linear in W), so `demix_filter` stays available in the loop.
 `algorithm_spatial in {'IP2', 'pairwise'}` (iva.py:544-599) is on the HIP path for AuxLaplaceIVA; AuxGaussIVA raises
 NotImplementedError for it exactly like the reference (iva.py:777-778).  There is no CPU fallback.
+
+`GradLaplaceIVA` and `NaturalGradLaplaceIVA` (iva.py:130-287) are the gradient baselines: two sweeps over X per iteration
+too (r_n(t), then the N x M cross-moment of the score with x or y per bin) and a per-bin step, in csrc/assx_gradbss.hip
+(DESIGN.md section 18); float64, one utterance, 2 <= n_channels <= 8.  `GradSteps` holds what they share with the FDICA
+classes of bss/fdica.py.
 """
 import numpy as np
 
@@ -140,6 +145,221 @@ class IVAbase(DeviceState):
 
     def compute_negative_loglikelihood(self):
         raise NotImplementedError("Implement 'compute_negative_loglikelihood' function.")
+
+
+class GradSteps:
+    """What the gradient models share -- GradIVAbase below and GradFDICAbase (bss/fdica.py): the refusals of `_reset`, one
+    update, the loss, and the loop as one library call.  float64, one utterance, 2..8 channels."""
+
+    _MODEL = None    # _lib.GRADBSS_IVA / _lib.GRADBSS_FDICA
+    _NATURAL = None  # False: gradient form, True: natural-gradient form; None: a base class without kernels
+    _MAX_BINS = None  # FDICA: what the permutation solver takes
+
+    def _reset(self, **kwargs):
+        assert self.input is not None, "Specify data!"
+
+        for key in kwargs.keys():
+            setattr(self, key, kwargs[key])
+
+        # refusals, before a device is touched
+        name = type(self).__name__
+        self._require_float64(self.dtype, complex_ok=True)
+        self.dtype = 'float64'
+        shape = self._shape_of(self.input)
+        if len(shape) != 3:
+            raise ValueError("{} takes one utterance (n_channels, n_bins, n_frames), got {} dims".format(name, len(shape)))
+        if not (self.input.is_complex() if isinstance(self.input, torch.Tensor) else np.iscomplexobj(self.input)):
+            raise ValueError("{} takes a complex input".format(name))
+        n_channels, n_bins, n_frames = shape
+        if not 2 <= n_channels <= 8:
+            raise ValueError("{} supports 2 <= n_channels <= 8, got n_channels={}".format(name, n_channels))
+        if n_bins < 1 or n_frames < 1:
+            raise ValueError("{}: empty input {}".format(name, shape))
+        if self._MAX_BINS is not None and n_bins > self._MAX_BINS:
+            raise ValueError("{} supports n_bins <= {}, got n_bins={}".format(name, self._MAX_BINS, n_bins))
+        if n_channels * n_bins * n_frames >= 1 << 28:
+            raise ValueError("{}: the input must stay below 4 GiB in complex128".format(name))
+        lr = self.lr
+        if isinstance(lr, (bool, np.bool_)) or not isinstance(lr, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(lr):
+            raise ValueError("lr must be a finite real number, got {!r}".format(lr))
+        ref = self.reference_id
+        if isinstance(ref, (bool, np.bool_)) or not isinstance(ref, (int, np.integer)) or not 0 <= ref < n_channels:
+            raise ValueError("reference_id must be an int in [0, {}), got {!r}".format(n_channels, ref))
+        self._check_warm_start_array('demix_filter', (n_bins, n_channels, n_channels), real=False)
+
+        eng = self._ensure_engine()
+        self._batched = False
+        self._X = self._upload(self.input, torch.complex128)
+        self._status = eng.new_status(1)
+        n_sources = n_channels  # n_channels == n_sources (iva.py:47, fdica.py:35)
+
+        self.n_sources, self.n_channels = n_sources, n_channels
+        self.n_bins, self.n_frames = n_bins, n_frames
+
+        if not hasattr(self, 'demix_filter'):
+            W = torch.eye(n_sources, n_channels, dtype=torch.complex128, device=eng.dev)
+            self._set_dev("W", W.repeat(1, n_bins, 1, 1).contiguous())
+        self._estimation = None
+        self._ws = eng.gradbss_workspace(n_channels, n_bins, n_frames)
+
+    def _fast_loop_ok(self):
+        """DeviceState's rule, and what assx_gradbss_iterate knows: a model with kernels, the holonomic natural form."""
+        return super()._fast_loop_ok() and self._NATURAL is not None and getattr(self, "is_holonomic", True)
+
+    def _run_fast_loop(self, iteration):
+        eng = self._engine
+        self._iterate_block(iteration + 1, ("W",), lambda loss: eng.gradbss_iterate(
+            iteration, self._MODEL, self._NATURAL, self._X[0], self._Wd[0], self._ws, lr=self.lr, eps=self.eps, loss=loss,
+            status=self._status))
+        self._estimation = None
+
+    def _loop(self, iteration):
+        """The loop of the reference's __call__ (iva.py:153-170, fdica.py:162-179)."""
+        if iteration > 0 and self._fast_loop_ok():
+            # nothing observes the model between iterations: the whole loop is ONE call into the library
+            # (assx_gradbss_iterate enqueues the kernels of the loop below in the same order: bit-identical)
+            self._run_fast_loop(iteration)
+            return
+
+        if self.recordable_loss:
+            self._record_loss()
+
+        if self.callbacks is not None:
+            for callback in self.callbacks:
+                callback(self)
+
+        for idx in range(iteration):
+            self.update_once()
+
+            if self.recordable_loss:
+                self._record_loss()
+
+            if self.callbacks is not None:
+                for callback in self.callbacks:
+                    callback(self)
+
+    def _grad_update(self):
+        self._engine.gradbss_update(self._MODEL, self._NATURAL, self._X[0], self._Wd[0], self._ws, lr=self.lr,
+                                    eps=self.eps, status=self._status)
+        self._touch("W")
+        self._estimation = None
+
+    def _loss_device(self):
+        return self._engine.gradbss_loss(self._MODEL, self._X[0], self._Wd[0], self._ws)
+
+    def _record_loss(self):
+        """Append the current loss without a host sync (the value stays in HBM until `loss` is read)."""
+        if isinstance(self.loss, LazyLossList) and self._own("compute_negative_loglikelihood"):
+            self.loss.append_device(self._loss_device(), False)
+        else:
+            self.loss.append(self.compute_negative_loglikelihood())
+
+    def _own(self, name):
+        """whether method `name` is still the model's own (the model: the first class that declares `_OWN_STEPS`)"""
+        owner = next(c for c in type(self).__mro__ if "_OWN_STEPS" in vars(c))
+        return getattr(type(self), name) is getattr(owner, name, None)
+
+    def _grad_loss(self):
+        loss = self._loss_device()
+        return np.float64(loss.item())
+
+    def _output(self, input, projection_back):
+        eng = self._engine
+        scale = None
+        if projection_back:
+            scale = eng.projection_back_scale(self._X, self._Wd, self.reference_id, self._status)
+        Y = eng.demix(self._X, self._Wd, scale=scale)
+        self._check_status()
+
+        output = self._unbatch(Y if isinstance(input, torch.Tensor) else to_numpy(Y, np.complex128))
+        self.estimation = output
+
+        return output
+
+
+class GradIVAbase(GradSteps, IVAbase):
+    """reference: iva.py:130-194"""
+
+    _MODEL = _lib.GRADBSS_IVA
+
+    def __init__(self, lr=1e-1, reference_id=0, callbacks=None, apply_projection_back=True, recordable_loss=True, eps=EPS,
+                 *, dtype='float64', device=None):
+        super().__init__(callbacks=callbacks, recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+        self._require_float64(dtype, complex_ok=True)
+
+        self.lr = lr
+        self.reference_id = reference_id
+        self.apply_projection_back = apply_projection_back
+
+    def __call__(self, input, iteration=100, **kwargs):
+        """
+        Args:
+            input (n_channels, n_bins, n_frames)
+        Returns:
+            output (n_channels, n_bins, n_frames)
+        """
+        self.input = input
+
+        self._reset(**kwargs)
+        self._loop(iteration)
+
+        return self._output(input, self.apply_projection_back)
+
+    def __repr__(self):
+        s = "GradIVA("
+        s += "lr={lr}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def update_once(self):
+        raise NotImplementedError("Implement 'update_once' function")
+
+    def compute_negative_loglikelihood(self):
+        raise NotImplementedError("Implement 'compute_negative_loglikelihood' function.")
+
+
+class GradLaplaceIVA(GradIVAbase):
+    """reference: iva.py:196-241"""
+    _NATURAL = False
+    _OWN_STEPS = ("update_once", "compute_negative_loglikelihood", "_record_loss")
+
+    def __repr__(self):
+        s = "NaturalGradIVA("
+        s += "lr={lr}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def update_once(self):
+        """iva.py:207-233: W <- W - lr ((1/T) sum_t phi x^H - W^-H)."""
+        self._grad_update()
+
+    def compute_negative_loglikelihood(self):
+        """iva.py:235-241.  Syncs to return a Python float."""
+        return self._grad_loss()
+
+
+class NaturalGradLaplaceIVA(GradIVAbase):
+    """reference: iva.py:243-287"""
+    _NATURAL = True
+    _OWN_STEPS = ("update_once", "compute_negative_loglikelihood", "_record_loss")
+
+    def __repr__(self):
+        s = "NaturalGradLaplaceIVA("
+        s += "lr={lr}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def update_once(self):
+        """iva.py:254-279: W <- W - lr ((1/T) sum_t phi y^H - I) W."""
+        self._grad_update()
+
+    def compute_negative_loglikelihood(self):
+        """iva.py:281-287.  Syncs to return a Python float."""
+        return self._grad_loss()
 
 
 class AuxIVAbase(IVAbase):

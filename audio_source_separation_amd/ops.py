@@ -19,7 +19,7 @@ _RAW = _lib.lib
 # array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
 # batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
 # read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF, the
-# two IPSDTA models and the covariance-domain MNMF passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# two IPSDTA models, the covariance-domain MNMF and the gradient IVA / FDICA entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
 # before anything is launched.
 def check_array(model, name, a, dtype, device, shape=None, numel=None):
     """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
@@ -996,6 +996,56 @@ class Engine:
         self._check(self._L.assx_covnmf_iterate(self.ctx, int(n_iter), 1 if normalize else 0, ptr(X), ptr(Tb), ptr(V),
                                                 ptr(H), float(eps), ptr(loss), ptr(status), ptr(ws), M, F, T, K, _lib.F64,
                                                 self._st()), "assx_covnmf_iterate")
+
+    # ------------------------------------------------------------------ gradient IVA / FDICA (bss/iva.py, bss/fdica.py)
+    def _gradbss_dims(self, X, W, ws=None, status=None):
+        if X.dim() != 3 or W.dim() != 3:
+            raise ValueError("GradBSS: expected input (M,F,T) and demix_filter (F,M,M), got %s and %s"
+                             % (tuple(X.shape), tuple(W.shape)))
+        M, F, T = (int(d) for d in X.shape)
+        self._args("GradBSS", (("input", X, (M, F, T), torch.complex128), ("demix_filter", W, (F, M, M), torch.complex128)))
+        self._arg("GradBSS", "status", status, torch.int32, numel=1)
+        if ws is not None:
+            check_workspace("GradBSS", ws, self.dev, self._L.assx_gradbss_workspace_bytes(M, F, T))
+        return M, F, T
+
+    def gradbss_workspace(self, M, F, T):
+        return self._new_workspace(self._L.assx_gradbss_workspace_bytes(M, F, T),
+                                   "GradBSS supports 2 <= n_channels <= 8 and an input below 4 GiB; got n_channels=%d, "
+                                   "n_bins=%d, n_frames=%d", M, F, T)
+
+    def gradbss_update(self, model, natural, X, W, ws, lr=0.1, eps=1e-12, status=None):
+        """One update of W (F,M,M) in place; model: _lib.GRADBSS_IVA / GRADBSS_FDICA."""
+        M, F, T = self._gradbss_dims(X, W, ws, status)
+        self._check(self._L.assx_gradbss_update(self.ctx, int(model), 1 if natural else 0, ptr(X), ptr(W), ptr(ws),
+                                                float(lr), float(eps), M, F, T, ptr(status), self._st()),
+                    "assx_gradbss_update")
+
+    def gradbss_loss(self, model, X, W, ws, loss=None):
+        """loss (1,) float64 of the W as it stands."""
+        M, F, T = self._gradbss_dims(X, W, ws)
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._arg("GradBSS", "loss", loss, torch.float64, numel=1)
+        self._check(self._L.assx_gradbss_loss(self.ctx, int(model), ptr(X), ptr(W), ptr(ws), ptr(loss), M, F, T,
+                                              self._st()), "assx_gradbss_loss")
+        return loss
+
+    def gradbss_iterate(self, n_iter, model, natural, X, W, ws, lr=0.1, eps=1e-12, loss=None, status=None):
+        """n_iter updates; loss: (n_iter + 1,) float64 (the loss before the loop and after every update) or None."""
+        M, F, T = self._gradbss_dims(X, W, ws, status)
+        self._arg("GradBSS", "loss", loss, torch.float64, numel=int(n_iter) + 1)
+        self._check(self._L.assx_gradbss_iterate(self.ctx, int(n_iter), int(model), 1 if natural else 0, ptr(X), ptr(W),
+                                                 ptr(ws), float(lr), float(eps), ptr(loss), M, F, T, ptr(status),
+                                                 self._st()), "assx_gradbss_iterate")
+
+    def fdica_solve_permutation(self, X, W, ws, eps=1e-12):
+        """FDICA's permutation solver on W (F,M,M) in place; returns (order (F,), perm (F,M)) int32."""
+        M, F, T = self._gradbss_dims(X, W, ws)
+        order = self.empty((F,), dtype=torch.int32)
+        perm = self.empty((F, M), dtype=torch.int32)
+        self._check(self._L.assx_fdica_solve_permutation(self.ctx, ptr(X), ptr(W), ptr(ws), ptr(order), ptr(perm),
+                                                         float(eps), M, F, T, self._st()), "assx_fdica_solve_permutation")
+        return order, perm
 
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):

@@ -593,6 +593,37 @@ int assx_covnmf_iterate(assx_ctx* ctx, int n_iter, int normalize, const void* X,
                         double* loss /* (n_iter,) or NULL */, int32_t* status, void* ws, int M, int F, int T, int K,
                         int dtype, void* stream);
 
+/* ---- (f13) gradient and natural-gradient Laplace IVA and FDICA (src/bss/iva.py:130-287, src/bss/fdica.py:8-301) -----------
+ * One utterance, float64: X (M,F,T) complex128, W (F,M,M) complex128 updated in place, N = M.  Envelope: 2 <= M <= 8,
+ * F, T >= 1, M F T < 2^28 (ASSX_E_UNSUPPORTED outside).  `ws` (assx_gradbss_workspace_bytes; 0 outside the envelope, no GPU
+ * needed) is scratch shared by all five entry points.  `status` is one word.  With y = W x:
+ *   model ASSX_GRADBSS_IVA    phi = y / max(sqrt(sum_f |y|^2), eps);  loss (2/T) sum_{n,t} sqrt(sum_f |y|^2) - 2 sum_f ln|det W_f|
+ *   model ASSX_GRADBSS_FDICA  phi = y / max(|y|, eps);                loss (2/T) sum_{n,f,t} |y| - 2 sum_f ln|det W_f|
+ *   natural 0                 W <- W - lr ((1/T) sum_t phi x^H - W^-H); an exactly singular W sets ASSX_STATUS_SINGULAR
+ *   natural 1                 W <- W - lr ((1/T) sum_t phi y^H - I) W
+ *   assx_gradbss_update             one update.
+ *   assx_gradbss_loss               loss[0] of the W as it stands.
+ *   assx_gradbss_iterate            n_iter updates; loss != NULL: loss[i] of the W before update i and loss[n_iter] of the
+ *                                   last one, enqueued without a synchronisation, bit for bit the single calls.
+ *   assx_fdica_solve_permutation    fdica.py:106-138: bins in ascending order of sum_t (sum_n P)^2 with
+ *                                   P = |y| / max(sqrt(sum_n |y|^2), eps) (equal values by index, NaN last); the first is the
+ *                                   criterion; every further bin takes the first permutation in lexicographic order with
+ *                                   the largest sum_{n,t} crit[n,t] P[pi(n),t], its rows of W are permuted and
+ *                                   crit += P[pi].  order (F) and perm (F,M) int32 are returned.  F <= 65536.
+ * A moment workgroup takes ASSX_GRADBSS_FRAME_CHUNK frames of one bin. */
+enum { ASSX_GRADBSS_IVA = 0, ASSX_GRADBSS_FDICA = 1 };
+#define ASSX_GRADBSS_FRAME_CHUNK 1024
+size_t assx_gradbss_workspace_bytes(int M, int F, int T);
+int assx_gradbss_update(assx_ctx* ctx, int model, int natural, const void* X, void* W, void* ws, double lr, double eps,
+                        int M, int F, int T, int32_t* status, void* stream);
+int assx_gradbss_loss(assx_ctx* ctx, int model, const void* X, const void* W, void* ws, double* loss /* (1,) */, int M,
+                      int F, int T, void* stream);
+int assx_gradbss_iterate(assx_ctx* ctx, int n_iter, int model, int natural, const void* X, void* W, void* ws, double lr,
+                         double eps, double* loss /* (n_iter + 1,) or NULL */, int M, int F, int T, int32_t* status,
+                         void* stream);
+int assx_fdica_solve_permutation(assx_ctx* ctx, const void* X, void* W, void* ws, int32_t* order /* (F) */,
+                                 int32_t* perm /* (F,M) */, double eps, int M, int F, int T, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
