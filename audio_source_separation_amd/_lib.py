@@ -24,6 +24,8 @@ STATUS_SINGULAR, STATUS_COND_REJECT, STATUS_NOT_CONVERGED = 1, 2, 4
 SPATIAL_IP, SPATIAL_ISS, SPATIAL_IP2 = 0, 1, 2
 GRADBSS_IVA, GRADBSS_FDICA = 0, 1
 GRADBSS_FRAME_CHUNK = 1024  # ASSX_GRADBSS_FRAME_CHUNK of include/assx.h: frames of one moment workgroup
+PDSBSS_LAPLACE = 0
+PDSBSS_FRAME_CHUNK = 1024  # ASSX_PDSBSS_FRAME_CHUNK of include/assx.h: frames of one sweep-2 workgroup
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -131,6 +133,15 @@ SIGNATURES = {
     "assx_gradbss_loss": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "assx_gradbss_iterate": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _d, _vp, _i, _i, _i, _vp, _vp]),
     "assx_fdica_solve_permutation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _vp]),
+    "assx_pdsbss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "assx_pdsbss_operator_norm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "assx_pdsbss_adjoint": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_pdsbss_prox_logdet": (_i, [_vp, _vp, _vp, _d, _i, _i, _vp, _vp]),
+    "assx_pdsbss_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_pdsbss_prox_group": (_i, [_vp, _i, _vp, _vp, _vp, _d, _d, _i, _i, _i, _vp]),
+    "assx_pdsbss_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _vp, _vp]),
+    "assx_pdsbss_loss": (_i, [_vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_pdsbss_iterate": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp]),
     "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

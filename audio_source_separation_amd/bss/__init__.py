@@ -3,7 +3,7 @@
 _EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta", "tIPSDTA": "ipsdta",
             "GradIVAbase": "iva", "GradLaplaceIVA": "iva", "NaturalGradLaplaceIVA": "iva",
             "FDICAbase": "fdica", "GradFDICAbase": "fdica", "GradLaplaceFDICA": "fdica",
-            "NaturalGradLaplaceFDICA": "fdica"}
+            "NaturalGradLaplaceFDICA": "fdica", "PDSBSSbase": "prox", "ProxLaplaceIVA": "iva"}
 __all__ = sorted(_EXPORTS)
 
 

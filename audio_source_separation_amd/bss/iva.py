@@ -15,6 +15,10 @@ NotImplementedError for it exactly like the reference (iva.py:777-778).  There i
 too (r_n(t), then the N x M cross-moment of the score with x or y per bin) and a per-bin step, in csrc/assx_gradbss.hip
 (DESIGN.md section 18); float64, one utterance, 2 <= n_channels <= 8.  `GradSteps` holds what they share with the FDICA
 classes of bss/fdica.py.
+
+`ProxLaplaceIVA` (iva.py:831-904) is IVA by primal-dual splitting on `PDSBSSbase` (bss/prox.py): a dual variable as large as
+the separated signal, a per-bin SVD and a frame-wise group shrinkage across all bins, in csrc/assx_pdsbss.hip (DESIGN.md
+section 19).
 """
 import numpy as np
 
@@ -22,6 +26,7 @@ from .._device import to_device, to_numpy, torch
 from .._state import DeviceArray, DeviceState
 from .._loss import LazyLossList
 from .. import _lib
+from .prox import PDSBSSbase
 
 EPS = 1e-12
 THRESHOLD = 1e+12
@@ -565,3 +570,60 @@ class AuxGaussIVA(AuxIVAbase):
     """reference: iva.py:621-802"""
     _KIND = _lib.IVA_GAUSS
     _NAME = "AuxGaussIVA"
+
+
+class ProxLaplaceIVA(PDSBSSbase):
+    """reference: iva.py:831-904"""
+
+    _PENALTY = _lib.PDSBSS_LAPLACE
+    _OWN_STEPS = PDSBSSbase._OWN_STEPS
+
+    def __init__(self, regularizer=1, step_prox_logdet=1e+0, step_prox_penalty=1e+0, step=1e+0, reference_id=0,
+                 callbacks=None, apply_projection_back=True, recordable_loss=True, eps=EPS, *, dtype='float64', device=None):
+        super().__init__(regularizer=regularizer, step_prox_logdet=step_prox_logdet, step_prox_penalty=step_prox_penalty,
+                         step=step, callbacks=callbacks, recordable_loss=recordable_loss, eps=eps, dtype=dtype, device=device)
+
+        self.reference_id = reference_id
+        self.apply_projection_back = apply_projection_back
+
+    def __call__(self, input, iteration, **kwargs):
+        """
+        Args:
+            input (n_channels, n_bins, n_frames)
+            iteration <int>
+        Returns:
+            output (n_channels, n_bins, n_frames)
+        """
+        self.input = input
+
+        self._reset(**kwargs)
+        self._loop(iteration)
+
+        return self._output(input, self.apply_projection_back)
+
+    def __repr__(self):
+        s = "ProxLaplaceIVA("
+        s += "regularizer={regularizer}, step_prox_logdet={step_prox_logdet}, step_prox_penalty={step_prox_penalty}"
+        s += ", step={step}"
+        s += ")"
+
+        return s.format(**self.__dict__)
+
+    def prox_penalty(self, z, mu=1):
+        """iva.py:867-889 on a dense (n_bins, n_sources, n_frames) array or device tensor: C max(0, 1 - mu / den) z with
+        den[n,t] = sqrt(sum_f |z|^2), mu where it is <= 0.  NumPy in, NumPy out; tensor in, tensor out."""
+        eng = self._ensure_engine()
+        zd = to_device(z, torch.complex128, eng.dev).contiguous()
+        if zd.dim() != 3:
+            raise ValueError("prox_penalty: expected z (n_bins, n_sources, n_frames), got {}".format(tuple(zd.shape)))
+        F, N, T = (int(d) for d in zd.shape)
+        ws = self._ws if (F, N, T) == (getattr(self, "n_bins", None), getattr(self, "n_sources", None),
+                                       getattr(self, "n_frames", None)) else eng.pdsbss_workspace(N, F, T)
+        out = eng.pdsbss_prox_group(zd, ws, C=float(self.regularizer), mu=float(mu), penalty=self._PENALTY)
+        if isinstance(z, torch.Tensor):
+            return out
+        return to_numpy(out, np.complex128)
+
+    def compute_penalty(self):
+        """iva.py:891-904: C sum_{n,t} sqrt(sum_f |y[n,f,t]|^2).  Syncs to return a Python float."""
+        return np.float64(self._loss_terms()[1][0].item())

@@ -19,7 +19,7 @@ _RAW = _lib.lib
 # array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
 # batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
 # read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF, the
-# two IPSDTA models, the covariance-domain MNMF and the gradient IVA / FDICA entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# two IPSDTA models, the covariance-domain MNMF, the gradient IVA / FDICA and the ProxLaplaceIVA entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
 # before anything is launched.
 def check_array(model, name, a, dtype, device, shape=None, numel=None):
     """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
@@ -1046,6 +1046,105 @@ class Engine:
         self._check(self._L.assx_fdica_solve_permutation(self.ctx, ptr(X), ptr(W), ptr(ws), ptr(order), ptr(perm),
                                                          float(eps), M, F, T, self._st()), "assx_fdica_solve_permutation")
         return order, perm
+
+    # ------------------------------------------------------------------ ProxLaplaceIVA (bss/prox.py, bss/iva.py)
+    def _pdsbss_dims(self, X, W=None, y=None, norm=None, ws=None, status=None):
+        if X.dim() != 3:
+            raise ValueError("PDSBSS: expected input (M,F,T), got %s" % (tuple(X.shape),))
+        M, F, T = (int(d) for d in X.shape)
+        self._args("PDSBSS", (("input", X, (M, F, T), torch.complex128),))
+        if W is not None:
+            self._args("PDSBSS", (("demix_filter", W, (F, M, M), torch.complex128),))
+        if y is not None:
+            self._args("PDSBSS", (("y", y, (F, M, T), torch.complex128),))
+        if norm is not None:
+            self._arg("PDSBSS", "norm", norm, torch.float64, numel=1)
+        self._arg("PDSBSS", "status", status, torch.int32, numel=1)
+        if ws is not None:
+            check_workspace("PDSBSS", ws, self.dev, self._L.assx_pdsbss_workspace_bytes(M, F, T))
+        return M, F, T
+
+    def pdsbss_workspace(self, M, F, T):
+        return self._new_workspace(self._L.assx_pdsbss_workspace_bytes(M, F, T),
+                                   "PDSBSS supports 2 <= n_channels <= 8 and an input below 4 GiB; got n_channels=%d, "
+                                   "n_bins=%d, n_frames=%d", M, F, T)
+
+    def pdsbss_operator_norm(self, X, ws, norm=None, status=None):
+        """norm (1,) float64 = max_f sigma_max(X_f); stays on the device."""
+        M, F, T = self._pdsbss_dims(X, ws=ws, status=status)
+        norm = norm if norm is not None else self.empty((1,), dtype=torch.float64)
+        self._arg("PDSBSS", "norm", norm, torch.float64, numel=1)
+        self._check(self._L.assx_pdsbss_operator_norm(self.ctx, ptr(X), ptr(ws), ptr(norm), M, F, T, ptr(status),
+                                                      self._st()), "assx_pdsbss_operator_norm")
+        return norm
+
+    def pdsbss_adjoint(self, X, norm, y, ws):
+        """G (F,M,M) = sum_t conj(X / norm) y."""
+        M, F, T = self._pdsbss_dims(X, y=y, norm=norm, ws=ws)
+        G = self.empty((F, M, M), dtype=torch.complex128)
+        self._check(self._L.assx_pdsbss_adjoint(self.ctx, ptr(X), ptr(norm), ptr(y), ptr(G), ptr(ws), M, F, T, self._st()),
+                    "assx_pdsbss_adjoint")
+        return G
+
+    def pdsbss_prox_logdet(self, W, mu=1.0, status=None):
+        """(F,M,M) -> (F,M,M): per bin U h(S) V^H of the SVD of W, h(s) = (s + sqrt(s^2 + 4 mu)) / 2."""
+        if W.dim() != 3 or W.shape[1] != W.shape[2]:
+            raise ValueError("PDSBSS: expected demix_filter (F,M,M), got %s" % (tuple(W.shape),))
+        F, M = int(W.shape[0]), int(W.shape[1])
+        self._arg("PDSBSS", "demix_filter", W, torch.complex128, shape=(F, M, M))
+        self._arg("PDSBSS", "status", status, torch.int32, numel=1)
+        out = self.empty((F, M, M), dtype=torch.complex128)
+        self._check(self._L.assx_pdsbss_prox_logdet(self.ctx, ptr(W), ptr(out), float(mu), M, F, ptr(status), self._st()),
+                    "assx_pdsbss_prox_logdet")
+        return out
+
+    def pdsbss_forward(self, X, norm, y, D):
+        """z (F,M,T) = y + (X / norm) D."""
+        M, F, T = self._pdsbss_dims(X, W=D, y=y, norm=norm)
+        z = self.empty((F, M, T), dtype=torch.complex128)
+        self._check(self._L.assx_pdsbss_forward(self.ctx, ptr(X), ptr(norm), ptr(y), ptr(D), ptr(z), M, F, T, self._st()),
+                    "assx_pdsbss_forward")
+        return z
+
+    def pdsbss_prox_group(self, z, ws, C=1.0, mu=1.0, penalty=_lib.PDSBSS_LAPLACE):
+        """(F,N,T) -> (F,N,T): C max(0, 1 - mu / den) z, den[n,t] = sqrt(sum_f |z|^2) (mu where it is <= 0)."""
+        if z.dim() != 3:
+            raise ValueError("PDSBSS: expected z (F,N,T), got %s" % (tuple(z.shape),))
+        F, N, T = (int(d) for d in z.shape)
+        self._arg("PDSBSS", "z", z, torch.complex128, shape=(F, N, T))
+        check_workspace("PDSBSS", ws, self.dev, self._L.assx_pdsbss_workspace_bytes(N, F, T))
+        out = self.empty((F, N, T), dtype=torch.complex128)
+        self._check(self._L.assx_pdsbss_prox_group(self.ctx, int(penalty), ptr(z), ptr(out), ptr(ws), float(C), float(mu), N,
+                                                   F, T, self._st()), "assx_pdsbss_prox_group")
+        return out
+
+    def pdsbss_update(self, X, norm, W, y, ws, C=1.0, mu1=1.0, mu2=1.0, alpha=1.0, status=None,
+                      penalty=_lib.PDSBSS_LAPLACE):
+        """One iteration on W (F,M,M) and y (F,M,T), both in place."""
+        M, F, T = self._pdsbss_dims(X, W, y, norm, ws, status)
+        self._check(self._L.assx_pdsbss_update(self.ctx, int(penalty), ptr(X), ptr(norm), ptr(W), ptr(y), ptr(ws), float(C),
+                                               float(mu1), float(mu2), float(alpha), M, F, T, ptr(status), self._st()),
+                    "assx_pdsbss_update")
+
+    def pdsbss_loss(self, X, W, ws, C=1.0, loss=None, terms=None, penalty=_lib.PDSBSS_LAPLACE):
+        """loss (1,) float64 of the W as it stands; terms (2,): the penalty and the negative log-determinant."""
+        M, F, T = self._pdsbss_dims(X, W, ws=ws)
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._arg("PDSBSS", "loss", loss, torch.float64, numel=1)
+        self._arg("PDSBSS", "terms", terms, torch.float64, numel=2)
+        self._check(self._L.assx_pdsbss_loss(self.ctx, int(penalty), ptr(X), ptr(W), ptr(ws), float(C), ptr(loss), ptr(terms),
+                                             M, F, T, self._st()), "assx_pdsbss_loss")
+        return loss
+
+    def pdsbss_iterate(self, n_iter, X, norm, W, y, ws, C=1.0, mu1=1.0, mu2=1.0, alpha=1.0, loss=None, status=None,
+                       penalty=_lib.PDSBSS_LAPLACE):
+        """n_iter iterations; loss: (n_iter + 1,) float64 (before the loop and after every iteration) or None."""
+        M, F, T = self._pdsbss_dims(X, W, y, norm, ws, status)
+        self._arg("PDSBSS", "loss", loss, torch.float64, numel=int(n_iter) + 1)
+        self._check(self._L.assx_pdsbss_iterate(self.ctx, int(n_iter), 0 if loss is None else 1, int(penalty), ptr(X),
+                                                ptr(norm), ptr(W), ptr(y), ptr(ws), float(C), float(mu1), float(mu2),
+                                                float(alpha), ptr(loss), M, F, T, ptr(status), self._st()),
+                    "assx_pdsbss_iterate")
 
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):

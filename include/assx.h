@@ -624,6 +624,51 @@ int assx_gradbss_iterate(assx_ctx* ctx, int n_iter, int model, int natural, cons
 int assx_fdica_solve_permutation(assx_ctx* ctx, const void* X, void* W, void* ws, int32_t* order /* (F) */,
                                  int32_t* perm /* (F,M) */, double eps, int M, int F, int T, void* stream);
 
+/* ---- (f14) ProxLaplaceIVA: IVA by primal-dual splitting (src/bss/prox.py:13-201, src/bss/iva.py:831-904) ---------------
+ * One utterance, float64: X (M,F,T) complex128, W (F,M,M) complex128 and the dual y (F,M,T) complex128 updated in place,
+ * N = M.  Envelope: 2 <= M <= 8, F, T >= 1, M F T < 2^28 (ASSX_E_UNSUPPORTED outside).  `ws` (assx_pdsbss_workspace_bytes; 0
+ * outside the envelope, no GPU needed) is scratch shared by the entry points that take one.  `norm` (1,) float64 lives in
+ * device memory and is read by the kernels: nothing here synchronises.  `status` is one word; an SVD that runs out of
+ * sweeps or meets a non-finite value sets ASSX_STATUS_NOT_CONVERGED.  `penalty`: ASSX_PDSBSS_LAPLACE, anything else is
+ * ASSX_E_ARG.  The reference's sparse block operator (prox.py:67-78) is dense per-bin algebra here; with Xn = X / norm:
+ *   assx_pdsbss_operator_norm   prox.py:67-76 (svds of the block operator): norm[0] = max_f sigma_max(X_f), X_f the (T,M)
+ *                               slice of bin f.
+ *   assx_pdsbss_adjoint         prox.py:121 (X.T.conj() @ y): G[f,n,m] = sum_t conj(Xn[m,f,t]) y[f,n,t], G (F,M,M).
+ *   assx_pdsbss_prox_logdet     prox.py:151-179: per bin the SVD U S V^H of Win, Wout = U h(S) V^H with
+ *                               h(s) = (s + sqrt(s^2 + 4 mu)) / 2; a rank-deficient Win gives a valid prox, not LAPACK's.
+ *   assx_pdsbss_forward         prox.py:122 (y + X @ (2 w_tilde - w)): z[f,n,t] = y[f,n,t] + sum_m Xn[m,f,t] D[f,n,m].
+ *   assx_pdsbss_prox_group      iva.py:867-889: den[n,t] = sqrt(sum_f |z|^2), mu where it is <= 0;
+ *                               out = C max(0, 1 - mu / den) z on an (F,N,T) array.
+ *   assx_pdsbss_update          prox.py:110-135, one iteration on (W, y): W~ = prox_logdet(W - mu1 mu2 G, mu1),
+ *                               z = forward(y, 2 W~ - W), y~ = z - prox_group(z, 1 / mu2), y <- alpha y~ + (1 - alpha) y,
+ *                               W <- alpha W~ + (1 - alpha) W.
+ *   assx_pdsbss_loss            prox.py:191-201, iva.py:891-904: loss[0] = C sum_{n,t} sqrt(sum_f |(W x)|^2) - sum_f ln|det W_f|
+ *                               with the unnormalised X; terms != NULL: terms[0] the penalty, terms[1] the negative
+ *                               log-determinant.
+ *   assx_pdsbss_iterate         prox.py:92-103: n_iter updates; record_loss 1: loss[0] of the W at entry and loss[i + 1]
+ *                               after update i, enqueued without a synchronisation, bit for bit update and loss in turn.
+ * A sweep-2 workgroup takes ASSX_PDSBSS_FRAME_CHUNK frames of one bin. */
+enum { ASSX_PDSBSS_LAPLACE = 0 };
+#define ASSX_PDSBSS_FRAME_CHUNK 1024
+size_t assx_pdsbss_workspace_bytes(int M, int F, int T);
+int assx_pdsbss_operator_norm(assx_ctx* ctx, const void* X, void* ws, double* norm /* (1,) */, int M, int F, int T,
+                              int32_t* status, void* stream);
+int assx_pdsbss_adjoint(assx_ctx* ctx, const void* X, const double* norm, const void* y, void* G /* (F,M,M) */, void* ws,
+                        int M, int F, int T, void* stream);
+int assx_pdsbss_prox_logdet(assx_ctx* ctx, const void* Win, void* Wout, double mu, int M, int F, int32_t* status,
+                            void* stream);
+int assx_pdsbss_forward(assx_ctx* ctx, const void* X, const double* norm, const void* y, const void* D /* (F,M,M) */,
+                        void* z /* (F,M,T) */, int M, int F, int T, void* stream);
+int assx_pdsbss_prox_group(assx_ctx* ctx, int penalty, const void* z, void* out, void* ws, double C, double mu, int N, int F,
+                           int T, void* stream);
+int assx_pdsbss_update(assx_ctx* ctx, int penalty, const void* X, const double* norm, void* W, void* y, void* ws, double C,
+                       double mu1, double mu2, double alpha, int M, int F, int T, int32_t* status, void* stream);
+int assx_pdsbss_loss(assx_ctx* ctx, int penalty, const void* X, const void* W, void* ws, double C, double* loss /* (1,) */,
+                     double* terms /* (2,) or NULL */, int M, int F, int T, void* stream);
+int assx_pdsbss_iterate(assx_ctx* ctx, int n_iter, int record_loss, int penalty, const void* X, const double* norm, void* W,
+                        void* y, void* ws, double C, double mu1, double mu2, double alpha,
+                        double* loss /* (n_iter + 1,) or NULL */, int M, int F, int T, int32_t* status, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
