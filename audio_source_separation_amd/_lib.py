@@ -26,6 +26,7 @@ GRADBSS_IVA, GRADBSS_FDICA = 0, 1
 GRADBSS_FRAME_CHUNK = 1024  # ASSX_GRADBSS_FRAME_CHUNK of include/assx.h: frames of one moment workgroup
 PDSBSS_LAPLACE = 0
 PDSBSS_FRAME_CHUNK = 1024  # ASSX_PDSBSS_FRAME_CHUNK of include/assx.h: frames of one sweep-2 workgroup
+BF_FRAME_CHUNK = 1024  # ASSX_BF_FRAME_CHUNK of include/assx.h: frames of one MDP workgroup
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -142,7 +143,13 @@ SIGNATURES = {
     "assx_pdsbss_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _i, _i, _vp, _vp]),
     "assx_pdsbss_loss": (_i, [_vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _i, _i, _i, _vp]),
     "assx_pdsbss_iterate": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp]),
-    "assx_projection_back_scale": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "assx_bf_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "assx_bf_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "assx_bf_ds_weights": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "assx_bf_ml_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _vp, _vp]),
+    "assx_pca_basis": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "assx_mdp_scale": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "assx_projection_back_scale":(_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_nmf_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),

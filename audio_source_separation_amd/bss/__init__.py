@@ -3,7 +3,8 @@
 _EXPORTS = {"GaussIPSDTA": "ipsdta", "IPSDTAbase": "ipsdta", "tIPSDTA": "ipsdta",
             "GradIVAbase": "iva", "GradLaplaceIVA": "iva", "NaturalGradLaplaceIVA": "iva",
             "FDICAbase": "fdica", "GradFDICAbase": "fdica", "GradLaplaceFDICA": "fdica",
-            "NaturalGradLaplaceFDICA": "fdica", "PDSBSSbase": "prox", "ProxLaplaceIVA": "iva"}
+            "NaturalGradLaplaceFDICA": "fdica", "PDSBSSbase": "prox", "ProxLaplaceIVA": "iva",
+            "DelaySumBeamformer": "beamform", "MVDRBeamformer": "beamform", "MaxSNRBeamformer": "beamform"}
 __all__ = sorted(_EXPORTS)
 
 

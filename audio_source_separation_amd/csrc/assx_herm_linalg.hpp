@@ -6,7 +6,8 @@
 // (__host__ __device__): the same code can be compiled for the host and checked against NumPy.
 //   herm_cholesky   A = L L^H, L lower with a real positive diagonal; false unless every pivot is > 0 and finite
 //   tri_inverse     L^{-1} of a lower-triangular L
-//   herm_sqrt_psd   (C)^{1/2} of a Hermitian C by cyclic Jacobi rotations, eigenvalues clamped at 0
+//   herm_jacobi     eigenvalues and eigenvectors of a Hermitian C by cyclic Jacobi rotations
+//   herm_sqrt_psd   (C)^{1/2} of a Hermitian C through herm_jacobi, eigenvalues clamped at 0
 //   herm_riccati    the positive-definite solution of H A H = B: the matrix geometric mean L^{-H} (L^H B L)^{1/2} L^{-1}
 //   unpack_herm     a Hermitian matrix from its M^2 packed reals
 #pragma once
@@ -147,12 +148,13 @@ __host__ __device__ inline void hermitize(Mat<M>& A) {
   }
 }
 
-// S = C^{1/2} for a Hermitian C (full storage), by cyclic Jacobi: C = U diag(w) U^H, S = U diag(sqrt(max(w, 0))) U^H.
-// C is destroyed.  At most 12 sweeps; a sweep stops the iteration once the off-diagonal mass is below 1e-32 of the
-// squared Frobenius norm.
+// The eigendecomposition C = U diag(w) U^H of a Hermitian C (full storage) by cyclic Jacobi: on return the diagonal of C
+// holds w (in no particular order) and the columns of U the eigenvectors.  At most 12 sweeps; a sweep stops the iteration
+// once the off-diagonal mass is below 1e-32 of the squared Frobenius norm.  Returns false when the sweeps ran out (or the
+// mass is not a number).  Used by herm_sqrt_psd below and by the PCA basis of csrc/assx_beamform.hip.
 template <int M>
-__host__ __device__ inline void herm_sqrt_psd(Mat<M>& C, Mat<M>& S) {
-  Mat<M>& U = S;  // eigenvectors first, then overwritten by the result
+__host__ __device__ inline bool herm_jacobi(Mat<M>& C, Mat<M>& U) {
+  bool done = false;
 #pragma unroll
   for (int i = 0; i < M; ++i)
 #pragma unroll
@@ -165,7 +167,10 @@ __host__ __device__ inline void herm_sqrt_psd(Mat<M>& C, Mat<M>& S) {
 #pragma unroll
       for (int j = 0; j < i; ++j) off += C.re[i][j] * C.re[i][j] + C.im[i][j] * C.im[i][j];
     }
-    if (!(off > 1e-32 * (tot + 2.0 * off))) break;
+    if (!(off > 1e-32 * (tot + 2.0 * off))) {
+      done = off == off;
+      break;
+    }
 #pragma unroll
     for (int p = 0; p < M - 1; ++p)
 #pragma unroll
@@ -202,6 +207,15 @@ __host__ __device__ inline void herm_sqrt_psd(Mat<M>& C, Mat<M>& S) {
         C.im[p][p] = 0.0, C.im[q][q] = 0.0;
       }
   }
+  return done;
+}
+
+// S = C^{1/2} for a Hermitian C (full storage): C = U diag(w) U^H by herm_jacobi, S = U diag(sqrt(max(w, 0))) U^H.
+// C is destroyed.
+template <int M>
+__host__ __device__ inline void herm_sqrt_psd(Mat<M>& C, Mat<M>& S) {
+  Mat<M>& U = S;  // eigenvectors first, then overwritten by the result
+  herm_jacobi(C, U);
   double w[M];
 #pragma unroll
   for (int i = 0; i < M; ++i) w[i] = C.re[i][i] > 0.0 ? sqrt(C.re[i][i]) : 0.0;

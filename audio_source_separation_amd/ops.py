@@ -19,7 +19,7 @@ _RAW = _lib.lib
 # array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
 # batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
 # read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF, the
-# two IPSDTA models, the covariance-domain MNMF, the gradient IVA / FDICA and the ProxLaplaceIVA entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# two IPSDTA models, the covariance-domain MNMF, the gradient IVA / FDICA, the ProxLaplaceIVA and the beamformer / PCA / MDP entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
 # before anything is launched.
 def check_array(model, name, a, dtype, device, shape=None, numel=None):
     """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
@@ -1145,6 +1145,76 @@ class Engine:
                                                 ptr(norm), ptr(W), ptr(y), ptr(ws), float(C), float(mu1), float(mu2),
                                                 float(alpha), ptr(loss), M, F, T, ptr(status), self._st()),
                     "assx_pdsbss_iterate")
+
+    # ------------------------------------------------------------------ beamformers, PCA, MDP (bss/beamform.py, ...)
+    def _bf_weights(self, A):
+        if A.dim() != 3:
+            raise ValueError("beamform: expected steering_vector (F,M,N), got %s" % (tuple(A.shape),))
+        F, M, N = (int(d) for d in A.shape)
+        self._arg("beamform", "steering_vector", A, torch.complex128, shape=(F, M, N))
+        return F, M, N, self.empty((F, N, M), dtype=torch.complex128), self.empty((F, N), dtype=torch.complex128)
+
+    def bf_workspace(self, C, N, F, T):
+        return self._new_workspace(self._L.assx_bf_workspace_bytes(C, N, F, T),
+                                   "MDP supports 1 to 8 reference channels and sources and arrays below 4 GiB; got "
+                                   "n_channels=%d, n_sources=%d, n_bins=%d, n_frames=%d", C, N, F, T)
+
+    def bf_apply(self, X, Wf, s=None):
+        """Y (N,F,T) = s[f,n] sum_m Wf[f,n,m] X[m,f,t] for X (M,F,T), Wf (F,N,M) and an optional s (F,N)."""
+        if X.dim() != 3 or Wf.dim() != 3:
+            raise ValueError("beamform: expected input (M,F,T) and a filter (F,N,M), got %s and %s"
+                             % (tuple(X.shape), tuple(Wf.shape)))
+        M, F, T = (int(d) for d in X.shape)
+        N = int(Wf.shape[1])
+        self._args("beamform", (("input", X, (M, F, T), torch.complex128), ("filter", Wf, (F, N, M), torch.complex128),
+                                ("scale", s, (F, N), torch.complex128)))
+        Y = self.empty((N, F, T), dtype=torch.complex128)
+        self._check(self._L.assx_bf_apply(self.ctx, ptr(X), ptr(Wf), ptr(s), ptr(Y), M, N, F, T, self._st()), "assx_bf_apply")
+        return Y
+
+    def bf_ds_weights(self, A, ref=0):
+        """(Wf (F,N,M), s (F,N)) of the delay-and-sum beamformer for steering vectors A (F,M,N)."""
+        F, M, N, Wf, s = self._bf_weights(A)
+        self._check(self._L.assx_bf_ds_weights(self.ctx, ptr(A), ptr(Wf), ptr(s), int(ref), M, N, F, self._st()),
+                    "assx_bf_ds_weights")
+        return Wf, s
+
+    def bf_ml_weights(self, A, R, ref=0, eps=1e-12, status=None):
+        """(Wf, s) of the ML beamformer for A (F,M,N) and a covariance R (F,M,M)."""
+        F, M, N, Wf, s = self._bf_weights(A)
+        self._arg("beamform", "covariance", R, torch.complex128, shape=(F, M, M))
+        self._arg("beamform", "status", status, torch.int32, numel=1)
+        self._check(self._L.assx_bf_ml_weights(self.ctx, ptr(A), ptr(R), ptr(Wf), ptr(s), int(ref), float(eps), M, N, F,
+                                               ptr(status), self._st()), "assx_bf_ml_weights")
+        return Wf, s
+
+    def pca_basis(self, C, status=None):
+        """(V (F,M,M), w (F,M) ascending, Wf (F,M,M) = V^H) of a Hermitian C (F,M,M)."""
+        if C.dim() != 3 or C.shape[1] != C.shape[2]:
+            raise ValueError("pca: expected covariance (F,M,M), got %s" % (tuple(C.shape),))
+        F, M = int(C.shape[0]), int(C.shape[1])
+        self._arg("pca", "covariance", C, torch.complex128, shape=(F, M, M))
+        self._arg("pca", "status", status, torch.int32, numel=1)
+        V, Wf = self.empty((F, M, M), dtype=torch.complex128), self.empty((F, M, M), dtype=torch.complex128)
+        w = self.empty((F, M), dtype=torch.float64)
+        self._check(self._L.assx_pca_basis(self.ctx, ptr(C), ptr(V), ptr(w), ptr(Wf), M, F, ptr(status), self._st()),
+                    "assx_pca_basis")
+        return V, w, Wf
+
+    def mdp_scale(self, Y, Xref, ws=None):
+        """scale (C,N,F) = sum_t conj(Y) Xref / sum_t |Y|^2 for Y (N,F,T) and Xref (C,F,T)."""
+        if Y.dim() != 3 or Xref.dim() != 3:
+            raise ValueError("MDP: expected Y (N,F,T) and a reference (C,F,T), got %s and %s"
+                             % (tuple(Y.shape), tuple(Xref.shape)))
+        N, F, T = (int(d) for d in Y.shape)
+        C = int(Xref.shape[0])
+        self._args("MDP", (("Y", Y, (N, F, T), torch.complex128), ("reference", Xref, (C, F, T), torch.complex128)))
+        ws = ws if ws is not None else self.bf_workspace(C, N, F, T)
+        check_workspace("MDP", ws, self.dev, self._L.assx_bf_workspace_bytes(C, N, F, T))
+        scale = self.empty((C, N, F), dtype=torch.complex128)
+        self._check(self._L.assx_mdp_scale(self.ctx, ptr(Y), ptr(Xref), ptr(scale), ptr(ws), C, N, F, T, self._st()),
+                    "assx_mdp_scale")
+        return scale
 
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):

@@ -669,6 +669,43 @@ int assx_pdsbss_iterate(assx_ctx* ctx, int n_iter, int record_loss, int penalty,
                         void* y, void* ws, double C, double mu1, double mu2, double alpha,
                         double* loss /* (n_iter + 1,) or NULL */, int M, int F, int T, int32_t* status, void* stream);
 
+/* ---- (f15) closed-form spatial filters: beamformers, PCA, MDP (src/bss/beamform.py:5-58, src/transform/pca.py:4-21,
+ * src/algorithm/minimum_distortion_principle.py:3-31) -----------------------------------------------------------------
+ * One utterance, float64: X (M,F,T) complex128, steering vectors A (F,M,N), a covariance (F,M,M), a filter Wf (F,N,M) with a
+ * scale s (F,N), Y (N,F,T); M channels and N sources need not be equal.  Envelope: 2 <= M <= 8, 1 <= N <= 8, F, T >= 1,
+ * max(M, N) F T < 2^28 (ASSX_E_UNSUPPORTED outside); 0 <= ref < M (ASSX_E_ARG).  `status` is one word.  Every sum has a
+ * fixed order and there is no float atomic.  The plain covariance mean_t x x^H that MVDR and PCA start from is
+ * assx_cov_accumulate with ASSX_W_NONE.
+ *   assx_bf_workspace_bytes  the scratch of assx_mdp_scale for C reference channels and N sources (0 outside
+ *                            1 <= C, N <= 8, max(C, N) F T < 2^28; no GPU needed); the other entry points need none.
+ *   assx_bf_apply            beamform.py:15-17, 39-42, pca.py:16: Y[n,f,t] = s[f,n] sum_m Wf[f,n,m] X[m,f,t], s may be NULL.
+ *   assx_bf_ds_weights       beamform.py:14-17: Wf[f,n,m] = conj(A[f,m,n]), s[f,n] = A[f,ref,n].
+ *   assx_bf_ml_weights       beamform.py:32-42: Num = R^-1 A (a general inverse with partial pivoting; an exactly zero pivot
+ *                            sets ASSX_STATUS_SINGULAR, numpy.linalg.inv raises there), den[n] = sum_m conj(A[m,n]) Num[m,n],
+ *                            den = eps where den < eps in NumPy's order of complex numbers (real parts first, imaginary
+ *                            parts on a tie), Wf[f,n,m] = Num[m,n] / den[n] (transposed, not conjugated), s[f,n] = A[f,ref,n].
+ *   assx_pca_basis           pca.py:15-16: per bin the eigenvectors V (F,M,M), one per column, and the eigenvalues w (F,M)
+ *                            ascending of the Hermitian C (F,M,M), read from its lower triangle, by cyclic Jacobi; equal
+ *                            eigenvalues keep the order of their Jacobi columns; every eigenvector carries the unit phase
+ *                            that makes its first entry real and non-negative; Wf[f,k,m] = conj(V[f,m,k]) for assx_bf_apply.
+ *                            Sweeps that run out, or a C that is not a number, set ASSX_STATUS_NOT_CONVERGED.
+ *   assx_mdp_scale           minimum_distortion_principle.py:24-26: scale[c,n,f] = sum_t conj(Y[n,f,t]) Xref[c,f,t] /
+ *                            sum_t |Y[n,f,t]|^2 for Xref (C,F,T), 1 <= C <= 8; the division is plain IEEE (a silent source
+ *                            bin gives NaN).
+ * An assx_mdp_scale workgroup takes ASSX_BF_FRAME_CHUNK frames of one bin. */
+#define ASSX_BF_FRAME_CHUNK 1024
+size_t assx_bf_workspace_bytes(int C, int N, int F, int T);
+int assx_bf_apply(assx_ctx* ctx, const void* X, const void* Wf /* (F,N,M) */, const void* s /* (F,N) or NULL */,
+                  void* Y /* (N,F,T) */, int M, int N, int F, int T, void* stream);
+int assx_bf_ds_weights(assx_ctx* ctx, const void* A /* (F,M,N) */, void* Wf, void* s, int ref, int M, int N, int F,
+                       void* stream);
+int assx_bf_ml_weights(assx_ctx* ctx, const void* A /* (F,M,N) */, const void* R /* (F,M,M) */, void* Wf, void* s, int ref,
+                       double eps, int M, int N, int F, int32_t* status, void* stream);
+int assx_pca_basis(assx_ctx* ctx, const void* C /* (F,M,M) */, void* V /* (F,M,M) */, double* w /* (F,M) */,
+                   void* Wf /* (F,M,M) */, int M, int F, int32_t* status, void* stream);
+int assx_mdp_scale(assx_ctx* ctx, const void* Y /* (N,F,T) */, const void* Xref /* (C,F,T) */, void* scale /* (C,N,F) */,
+                   void* ws, int C, int N, int F, int T, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
