@@ -27,6 +27,7 @@ GRADBSS_FRAME_CHUNK = 1024  # ASSX_GRADBSS_FRAME_CHUNK of include/assx.h: frames
 PDSBSS_LAPLACE = 0
 PDSBSS_FRAME_CHUNK = 1024  # ASSX_PDSBSS_FRAME_CHUNK of include/assx.h: frames of one sweep-2 workgroup
 BF_FRAME_CHUNK = 1024  # ASSX_BF_FRAME_CHUNK of include/assx.h: frames of one MDP workgroup
+IDLMA_FRAME_CHUNK = 1024  # ASSX_IDLMA_FRAME_CHUNK of include/assx.h: frames of one workgroup of IDLMA's pass over X
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -149,6 +150,12 @@ SIGNATURES = {
     "assx_bf_ml_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _vp, _vp]),
     "assx_pca_basis": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "assx_mdp_scale": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "assx_idlma_workspace_bytes": (_sz, [_i, _i, _i]),
+    "assx_idlma_dnn_input": (_i, [_vp, _vp, _vp, _d, _vp, _i, _i, _i, _vp]),
+    "assx_idlma_variance": (_i, [_vp, _vp, _d, _d, _d, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_idlma_normalize_pb": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "assx_idlma_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "assx_idlma_step": (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "assx_projection_back_scale":(_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_projection_back": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "assx_compute_demix_filter": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -19,7 +19,7 @@ _RAW = _lib.lib
 # array of another shape, dtype or device, or a strided view -- a separate() input longer than the fitted activation, a
 # batched input on an unbatched model, a reassigned attribute, a float32 `loss`, a `status` left on the CPU -- would be
 # read or written past its end.  Every array and workspace of FastMNMF, MNMF, ComplexEUCNMF, EUCNTF, LDPSDTF, the
-# two IPSDTA models, the covariance-domain MNMF, the gradient IVA / FDICA, the ProxLaplaceIVA and the beamformer / PCA / MDP entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
+# two IPSDTA models, the covariance-domain MNMF, the gradient IVA / FDICA, the ProxLaplaceIVA, the beamformer / PCA / MDP and the IDLMA entry points passes one of the two checks below, where all of that is still known, and is refused with ValueError
 # before anything is launched.
 def check_array(model, name, a, dtype, device, shape=None, numel=None):
     """`a` must be a contiguous `dtype` tensor on `device`: of exactly `shape`, or (shape None) of at least `numel`
@@ -1215,6 +1215,72 @@ class Engine:
         self._check(self._L.assx_mdp_scale(self.ctx, ptr(Y), ptr(Xref), ptr(scale), ptr(ws), C, N, F, T, self._st()),
                     "assx_mdp_scale")
         return scale
+
+    # ------------------------------------------------------------------ GaussIDLMA around its network (sss/idlma.py)
+    def _idlma_dims(self, X, W, ws=None, status=None, **maps):
+        """(M, F, T) of X (M,F,T) and W (F,M,M); maps: name -> ((N,F,T) tensor or None, its dtype)."""
+        if X.dim() != 3:
+            raise ValueError("IDLMA: expected input (M,F,T), got %s" % (tuple(X.shape),))
+        M, F, T = (int(d) for d in X.shape)
+        self._args("IDLMA", (("input", X, (M, F, T), torch.complex128), ("demix_filter", W, (F, M, M), torch.complex128)))
+        for name, (a, dtype) in maps.items():
+            self._arg("IDLMA", name, a, dtype, shape=(M, F, T))
+        self._arg("IDLMA", "status", status, torch.int32, numel=1)
+        if ws is not None:
+            check_workspace("IDLMA", ws, self.dev, self._L.assx_idlma_workspace_bytes(M, F, T))
+        return M, F, T
+
+    def idlma_workspace(self, M, F, T):
+        return self._new_workspace(self._L.assx_idlma_workspace_bytes(M, F, T),
+                                   "IDLMA supports 2 <= n_channels <= 8, n_frames >= n_channels and an input below 4 GiB; "
+                                   "got n_channels=%d, n_bins=%d, n_frames=%d", M, F, T)
+
+    def idlma_dnn_input(self, X, W, domain=2, out=None):
+        """The network's input (N,F,T) float32 = (|W_f x|^2)^(domain/2) for X (M,F,T) and W (F,N,M)."""
+        M, F, T = self._idlma_dims(X, W, dnn_input=(out, torch.float32))
+        out = out if out is not None else self.empty((M, F, T), dtype=torch.float32)
+        self._check(self._L.assx_idlma_dnn_input(self.ctx, ptr(X), ptr(W), float(domain), ptr(out), M, F, T, self._st()),
+                    "assx_idlma_dnn_input")
+        return out
+
+    def idlma_variance(self, network_output, dnn_output, R, domain=2, dnn_flooring=1e-5, eps=1e-12):
+        """dnn_output (N,F,T) float32 from the network's float32 output (None: dnn_output is read as it stands) and the
+        variance R (N,F,T) float64, both written in place."""
+        if dnn_output.dim() != 3:
+            raise ValueError("IDLMA: expected dnn_output (N,F,T), got %s" % (tuple(dnn_output.shape),))
+        N, F, T = (int(d) for d in dnn_output.shape)
+        self._args("IDLMA", (("network_output", network_output, (N, F, T), torch.float32),
+                             ("dnn_output", dnn_output, (N, F, T), torch.float32), ("R", R, (N, F, T), torch.float64)))
+        self._check(self._L.assx_idlma_variance(self.ctx, ptr(network_output), float(domain), float(dnn_flooring), float(eps),
+                                                ptr(dnn_output), ptr(R), N, F, T, self._st()), "assx_idlma_variance")
+
+    def idlma_normalize_pb(self, W, scale):
+        """W (F,N,M) in place: W[f,n,:] *= scale[n,f] for scale (N,F)."""
+        if W.dim() != 3 or W.shape[1] != W.shape[2]:
+            raise ValueError("IDLMA: expected demix_filter (F,M,M), got %s" % (tuple(W.shape),))
+        F, M = int(W.shape[0]), int(W.shape[1])
+        self._args("IDLMA", (("demix_filter", W, (F, M, M), torch.complex128), ("scale", scale, (M, F), torch.complex128)))
+        self._check(self._L.assx_idlma_normalize_pb(self.ctx, ptr(W), ptr(scale), M, F, self._st()), "assx_idlma_normalize_pb")
+
+    def idlma_loss(self, X, W, R, ws, loss=None):
+        """loss (1,) float64 of W (F,N,M) and the variance R (N,F,T) float64."""
+        M, F, T = self._idlma_dims(X, W, ws=ws, R=(R, torch.float64))
+        loss = loss if loss is not None else self.empty((1,), dtype=torch.float64)
+        self._arg("IDLMA", "loss", loss, torch.float64, numel=1)
+        self._check(self._L.assx_idlma_loss(self.ctx, ptr(X), ptr(W), ptr(R), ptr(loss), ptr(ws), M, F, T, self._st()),
+                    "assx_idlma_loss")
+        return loss
+
+    def idlma_step(self, X, W, network_output, dnn_output, ws, domain=2, dnn_flooring=1e-5, eps=1e-12, threshold=1e12, ref=0,
+                   loss=None, next_input=None, status=None):
+        """Everything between two evaluations of the network in one call: W (F,N,M) and dnn_output (N,F,T) float32 in place,
+        loss (1,) float64 of the updated model and the network's next input (N,F,T) float32 where given."""
+        M, F, T = self._idlma_dims(X, W, ws=ws, status=status, network_output=(network_output, torch.float32),
+                                   dnn_output=(dnn_output, torch.float32), next_input=(next_input, torch.float32))
+        self._arg("IDLMA", "loss", loss, torch.float64, numel=1)
+        self._check(self._L.assx_idlma_step(self.ctx, ptr(X), ptr(W), ptr(network_output), float(domain), float(dnn_flooring),
+                                            float(eps), float(threshold), int(ref), ptr(dnn_output), ptr(loss),
+                                            ptr(next_input), ptr(status), ptr(ws), M, F, T, self._st()), "assx_idlma_step")
 
     # ------------------------------------------------------------------ projection back
     def projection_back_scale(self, X, W, ref=0, status=None):

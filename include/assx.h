@@ -706,6 +706,43 @@ int assx_pca_basis(assx_ctx* ctx, const void* C /* (F,M,M) */, void* V /* (F,M,M
 int assx_mdp_scale(assx_ctx* ctx, const void* Y /* (N,F,T) */, const void* Xref /* (C,F,T) */, void* scale /* (C,N,F) */,
                    void* ws, int C, int N, int F, int T, void* stream);
 
+/* ---- GaussIDLMA around its network (src/sss/idlma.py:89-246) --------------------------------------------------------
+ * The DNN source model stays with the host (a torch module); these calls are everything else of an iteration.  float64
+ * state, ONE utterance, 2 <= M <= 8, N = M, F >= 1, T >= M (below that the reference inverts a singular X X^H): other
+ * sizes are refused with ASSX_E_UNSUPPORTED, a domain outside [1, 2] with ASSX_E_ARG.  X (M,F,T) and W (F,N,M) complex128;
+ * the network's input and output and dnn_output are (N,F,T) float32, R (N,F,T) float64 holding widened float32 values,
+ * scale (N,F) complex128, loss one float64.  Every sum has a fixed order; no float atomics.
+ * A workgroup of the pass over X takes ASSX_IDLMA_FRAME_CHUNK frames of one bin, a thread four consecutive ones.
+ *   assx_idlma_dnn_input     idlma.py:165-167, 214, 217: input = float32((|W_f x|^2)^(domain/2)), |.|^2 in float64; the
+ *                            power is exact for domain 2, sqrt for domain 1, pow otherwise.
+ *   assx_idlma_variance      idlma.py:223, 230 and 183, 189 (= 242-243) in NumPy's float32 arithmetic: dnn_output =
+ *                            network_output^(2/domain), floored at float32(dnn_flooring) unless that is 0; R =
+ *                            dnn_output^(2/domain) -- the exponent a second time, as the reference applies it -- floored at
+ *                            float32(eps) and widened.  Exponent 1 is the identity, 2 a float32 multiply, others powf.  NaN
+ *                            passes both floors.  network_output = NULL: dnn_output is read as it stands, only R is written.
+ *   assx_idlma_normalize_pb  idlma.py:151-155 in its scaled form: W[f,n,:] *= scale[n,f] (scale of
+ *                            assx_projection_back_scale); algebraically the reference's refit (Y scale) X^H (X X^H)^-1.
+ *   assx_idlma_loss          idlma.py:233-246: sum (|y|^2 / R + log R) - 2 T sum_f log|det W_f|, log R the float64
+ *                            logarithm rounded to float32 (the reference takes a float32 logarithm).
+ *   assx_idlma_step          everything between two evaluations of the network, enqueued without a synchronisation:
+ *                            assx_idlma_variance, assx_idlma_space_update on R (idlma.py:175-210), the projection-back
+ *                            scale for channel `ref`, assx_idlma_normalize_pb, then ONE pass over X that gives loss[0] of the
+ *                            updated model (loss != NULL) and the network's next input (next_input != NULL): bit for bit what
+ *                            assx_idlma_loss and assx_idlma_dnn_input give alone.  R and scale live in ws.
+ * `ws`: assx_idlma_workspace_bytes(M, F, T) bytes (0 outside the envelope; needs no GPU). */
+#define ASSX_IDLMA_FRAME_CHUNK 1024
+size_t assx_idlma_workspace_bytes(int M, int F, int T);
+int assx_idlma_dnn_input(assx_ctx* ctx, const void* X, const void* W, double domain, float* input, int M, int F, int T,
+                         void* stream);
+int assx_idlma_variance(assx_ctx* ctx, const float* network_output, double domain, double dnn_flooring, double eps,
+                        float* dnn_output, double* R, int M, int F, int T, void* stream);
+int assx_idlma_normalize_pb(assx_ctx* ctx, void* W, const void* scale, int M, int F, void* stream);
+int assx_idlma_loss(assx_ctx* ctx, const void* X, const void* W, const double* R, double* loss, void* ws, int M, int F,
+                    int T, void* stream);
+int assx_idlma_step(assx_ctx* ctx, const void* X, void* W, const float* network_output, double domain, double dnn_flooring,
+                    double eps, double threshold, int ref, float* dnn_output, double* loss, float* next_input,
+                    int32_t* status, void* ws, int M, int F, int T, void* stream);
+
 /* ---- (a8) projection back --------------------------------------------------------------- */
 /* projection_back(Y, reference) for a 2-D reference (src/algorithm/projection_back.py:13-21) with
  * Y = W X formed on the fly and reference = X[ref]:  scale[b,n,f] = (x_ref Y^H (Y Y^H)^{-1})[n]. */
