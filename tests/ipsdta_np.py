@@ -294,6 +294,7 @@ def update_activation(X, W, basis, H, eps, n_blocks, la=LAPACK, diag=None):
     if diag is not None:
         diag["num_floored"] = bool(np.any(num < 0.0))
         diag["den_floored"] = bool(np.any(den < eps))
+        diag["num_min"], diag["den_min"] = float(np.min(num)), float(np.min(den))
     return H * np.sqrt(np.maximum(num, 0.0) / np.maximum(den, eps))
 
 
@@ -363,18 +364,20 @@ def spatial_sweep(X, W, Ri_parts, Q, eps, n_blocks, diag=None):
                 if diag is not None and nb > 1:
                     a = np.abs(eta_hat)  # exactly 0 for a diagonal model (gamma is exactly 0 there): far from the switch
                     diag["eta_hat_min"] = min(diag.get("eta_hat_min", np.inf), float(np.min(a[a > 0.0], initial=np.inf)))
+                if diag is not None:
+                    diag["eta_min"] = min(diag.get("eta_min", np.inf), float(np.min(np.abs(eta))))
                 Wp[:, i, src, :] = np.conj(weight[:, None] * zeta - zeta_hat)
         W[f0:f0 + n * nb] = Wp.reshape(n * nb, M, M)
     return W
 
 
-def update_spatial(X, W, basis, H, eps, n_blocks, n_sweeps, la=LAPACK, each=False):
+def update_spatial(X, W, basis, H, eps, n_blocks, n_sweeps, la=LAPACK, each=False, diag=None):
     """n_sweeps VCD sweeps on hoisted Ri and Q; each=True returns the list of W after every sweep"""
     Ri = inverse_parts(basis, H, eps, la)
     Q = q_matrices(X, Ri, eps, n_blocks, la)
     out = []
     for _ in range(n_sweeps):
-        W = spatial_sweep(X, W, Ri, Q, eps, n_blocks)
+        W = spatial_sweep(X, W, Ri, Q, eps, n_blocks, diag=diag)
         out.append(W)
     return out if each else W
 

@@ -109,6 +109,7 @@ def update_activation(X, W, basis, H, eps, n_blocks, nu, la=LAPACK, diag=None):
     if diag is not None:
         diag["num_floored"] = bool(np.any(num < 0.0))
         diag["den_floored"] = bool(np.any(den < eps))
+        diag["num_min"], diag["den_min"] = float(np.min(num)), float(np.min(den))
     return H * np.sqrt(np.maximum(num, 0.0) / np.maximum(den, eps))
 
 
@@ -169,6 +170,8 @@ def spatial_sweep(X, W, Ri_parts, XX, eps, n_blocks, nu, la=LAPACK, diag=None, f
                 if diag is not None and nb > 1:
                     a = np.abs(eta_hat)
                     diag["eta_hat_min"] = min(diag.get("eta_hat_min", np.inf), float(np.min(a[a > 0.0], initial=np.inf)))
+                if diag is not None:
+                    diag["eta_min"] = min(diag.get("eta_min", np.inf), float(np.min(np.abs(eta))))
                 W[bins, src, :] = np.conj(weight[:, None] * zeta - zeta_hat)
     return W
 

@@ -23,6 +23,12 @@ update: nothing is written then.
 
     python tools/ipsdta_tolerance_probe.py --model gauss|t            # writes tolerances.json
     python tools/ipsdta_tolerance_probe.py --model gauss|t --check    # measures and compares with the committed file
+    python tools/ipsdta_tolerance_probe.py --envelope                 # the d tables of tests/ipsdta_envelope_np.py
+
+`--envelope` needs neither the reference tree nor a fixture: over the grid of tests/ipsdta_envelope_np.py and for both
+models it measures, per entry point, the LAPACK restatement against the restatement on the kernels' algorithms and against
+itself after a one-ulp move of everything it reads (ipsdta_envelope_np.measure), prints the figures per case and the
+tables D and D_BASIS_SINGLE_FRAME as that module commits them, and compares them with the committed ones.
 
 Below, nu is None for the Gauss model and the fixture's degree of freedom for the t model; the restatements take it after
 n_blocks.
@@ -40,14 +46,20 @@ import numpy as np  # noqa: E402
 
 import ipsdta_np as ip  # noqa: E402
 import tipsdta_np as tp  # noqa: E402
-import make_golden  # noqa: E402,F401  reference on sys.path
-from bss.ipsdta import GaussIPSDTA, tIPSDTA  # noqa: E402
-from algorithm.projection_back import projection_back  # noqa: E402
+
+GaussIPSDTA = tIPSDTA = projection_back = None  # the reference's, bound by load_reference()
 
 FACTOR = 16
 LIMIT = 1e-9
 RESOLUTION = 2.0 ** -52
 N_DRAWS = 3
+
+
+def load_reference():
+    global GaussIPSDTA, tIPSDTA, projection_back
+    import make_golden  # noqa: F401  reference on sys.path
+    from bss.ipsdta import GaussIPSDTA, tIPSDTA
+    from algorithm.projection_back import projection_back
 
 
 def restatement(nu):
@@ -229,11 +241,39 @@ def probe(rs):
     return doc
 
 
+def envelope():
+    """Measure the d tables of tests/ipsdta_envelope_np.py; exit status 1 where they differ from the committed ones."""
+    import ipsdta_envelope_np as ev
+    outputs = ("basis", "activation", "normalize_U", "normalize_H", "spatial_1", "spatial_2", "loss")
+    print("%-20s %-5s " % ("case", "model") + " ".join("%-11s" % o for o in outputs))
+
+    def report(name, model, d):
+        print("%-20s %-5s " % (name, model) + " ".join("%-11s" % ("%.1e" % d[o] if o in d else "-") for o in outputs),
+              flush=True)
+
+    worst, own = ev.measure_grid(report=report)
+    D = {m: {k: ev.round_up(v) for k, v in worst[m].items()} for m in worst}
+    S = {m: {c: ev.round_up(v) for c, v in own[m].items()} for m in own}
+    for m in D:
+        print("D[%r] = %r" % (m, D[m]))
+    for m in S:
+        print("D_BASIS_SINGLE_FRAME[%r] = %r" % (m, S[m]))
+    same = D == ev.D and S == ev.D_BASIS_SINGLE_FRAME
+    print("the committed tables are %s" % ("reproduced" if same else "DIFFERENT"))
+    sys.exit(0 if same else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("gauss", "t"), required=True)
+    ap.add_argument("--model", choices=("gauss", "t"))
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--envelope", action="store_true")
     a = ap.parse_args()
+    if a.envelope:
+        envelope()
+    if a.model is None:
+        ap.error("--model or --envelope is required")
+    load_reference()
     rs = ip if a.model == "gauss" else tp
     out = os.path.join(rs.GOLDEN, "tolerances.json")
     doc = probe(rs)
