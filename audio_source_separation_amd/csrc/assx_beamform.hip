@@ -19,18 +19,16 @@
 // The plain covariance of MVDR and PCA is assx_cov_accumulate with ASSX_W_NONE; nothing here forms one.
 //
 // Every sum has a fixed order and there is no float atomic: two runs give the same bits.
-#include "assx_common.hpp"
-#include "assx_small_linalg.hpp"
 #include "assx_herm_linalg.hpp"
-#include "assx_factor_common.hpp"
+#include "assx_perbin_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
+using namespace assx::pb;
 
 namespace {
 
 constexpr int BF_CHUNK = ASSX_BF_FRAME_CHUNK;  // frames of one MDP workgroup
-constexpr int BF_NW = BLK / WAVE;
 
 static_assert(BF_CHUNK % BLK == 0, "a chunk is whole trips of the workgroup");
 
@@ -48,7 +46,7 @@ inline bool mdp_in_envelope(int C, int N, int F, int T) {
   return C >= 1 && C <= 8 && N >= 1 && N <= NMAX && bf_sizes_ok(C > N ? C : N, F, T);
 }
 
-inline int bf_chunks(int T) { return (T + BF_CHUNK - 1) / BF_CHUNK; }
+inline int bf_chunks(int T) { return chunks(T, BF_CHUNK); }
 
 // part (F, chunks, C, N, 3): Re and Im of sum_t conj(Y) X and sum_t |Y|^2 of one chunk
 inline size_t mdp_ws_bytes(int C, int N, int F, int T) {
@@ -67,8 +65,7 @@ __global__ void __launch_bounds__(BLK) bf_apply_kernel(const Cd* __restrict__ X,
   const int f = blockIdx.x / NTILE, t = (blockIdx.x % NTILE) * BLK + threadIdx.x;
   if (t >= T) return;
   Cd x[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = tocx(ldv(X + ((size_t)m * F + f) * T + t));
+  load_frame<M>(X, f, t, F, T, x);
   const Cd* Wb = Wf + (size_t)f * N * M;
   for (int n = 0; n < N; ++n) {
     Cd y = cmake<double>(0.0, 0.0);
@@ -170,13 +167,13 @@ __global__ void __launch_bounds__(WAVE) pca_basis_kernel(const Cd* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(BLK) mdp_partial_kernel(const Cd* __restrict__ Y, const Cd* __restrict__ Xr,
                                                           double* __restrict__ part, int C, int N, int F, int T, int CH) {
-  __shared__ double red[BF_NW][NMAX * 3];
+  __shared__ double red[NW][NMAX * 3];
   const int c = blockIdx.x % C, ch = blockIdx.x / C % CH, f = blockIdx.x / C / CH;
   const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
   double ar[NMAX], ai[NMAX], ap[NMAX];
 #pragma unroll
   for (int n = 0; n < NMAX; ++n) ar[n] = 0.0, ai[n] = 0.0, ap[n] = 0.0;
-  const int t_end = T - ch * BF_CHUNK < BF_CHUNK ? T : (ch + 1) * BF_CHUNK;
+  const int t_end = chunk_end(ch, BF_CHUNK, T);
   for (int t = ch * BF_CHUNK + tid; t < t_end; t += BLK) {
     const Cd x = tocx(ldv(Xr + ((size_t)c * F + f) * T + t));
 #pragma unroll
@@ -197,7 +194,7 @@ __global__ void __launch_bounds__(BLK) mdp_partial_kernel(const Cd* __restrict__
   __syncthreads();
   if (tid < N * 3) {  // the waves in index order
     double v = red[0][tid];
-    for (int q = 1; q < BF_NW; ++q) v += red[q][tid];
+    for (int q = 1; q < NW; ++q) v += red[q][tid];
     part[(size_t)blockIdx.x * N * 3 + tid] = v;
   }
 }
@@ -244,12 +241,9 @@ int assx_bf_apply(assx_ctx* ctx, const void* X, const void* Wf, const void* s, v
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && Wf && Y, ASSX_E_NULL, "assx_bf_apply: NULL array");
   const int ntile = (int)nblocks(T, BLK);
-  return dispatch_channels(ctx, "assx_bf_apply", M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((bf_apply_kernel<MC>), dim3((unsigned)F * ntile), dim3(BLK), 0, (hipStream_t)stream, (const Cd*)X,
-                       (const Cd*)Wf, (const Cd*)s, (Cd*)Y, N, F, T, ntile);
-    ASSX_LAUNCH_CHECK(ctx, "bf_apply_kernel");
-    return 0;
+  return launch_for_channels(ctx, "assx_bf_apply", "bf_apply_kernel", M, [&](auto mt) {
+    hipLaunchKernelGGL((bf_apply_kernel<decltype(mt)::value>), dim3((unsigned)F * ntile), dim3(BLK), 0, (hipStream_t)stream,
+                       (const Cd*)X, (const Cd*)Wf, (const Cd*)s, (Cd*)Y, N, F, T, ntile);
   });
 }
 
@@ -271,12 +265,9 @@ int assx_bf_ml_weights(assx_ctx* ctx, const void* A, const void* R, void* Wf, vo
   if (rc) return rc;
   ASSX_REQUIRE(ctx, ref >= 0 && ref < M, ASSX_E_ARG, "reference_id must be in [0, %d), got %d", M, ref);
   ASSX_REQUIRE(ctx, A && R && Wf && s, ASSX_E_NULL, "assx_bf_ml_weights: NULL array");
-  return dispatch_channels(ctx, "assx_bf_ml_weights", M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((bf_ml_weights_kernel<MC>), dim3(nblocks(F, WAVE)), dim3(WAVE), 0, (hipStream_t)stream, (const Cd*)A,
-                       (const Cd*)R, (Cd*)Wf, (Cd*)s, ref, eps, N, F, status);
-    ASSX_LAUNCH_CHECK(ctx, "bf_ml_weights_kernel");
-    return 0;
+  return launch_for_channels(ctx, "assx_bf_ml_weights", "bf_ml_weights_kernel", M, [&](auto mt) {
+    hipLaunchKernelGGL((bf_ml_weights_kernel<decltype(mt)::value>), dim3(nblocks(F, WAVE)), dim3(WAVE), 0,
+                       (hipStream_t)stream, (const Cd*)A, (const Cd*)R, (Cd*)Wf, (Cd*)s, ref, eps, N, F, status);
   });
 }
 
@@ -284,12 +275,9 @@ int assx_pca_basis(assx_ctx* ctx, const void* C, void* V, double* w, void* Wf, i
   int rc = bf_check(ctx, "assx_pca_basis", M, M, F, 1);
   if (rc) return rc;
   ASSX_REQUIRE(ctx, C && V && w && Wf, ASSX_E_NULL, "assx_pca_basis: NULL array");
-  return dispatch_channels(ctx, "assx_pca_basis", M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((pca_basis_kernel<MC>), dim3(nblocks(F, WAVE)), dim3(WAVE), 0, (hipStream_t)stream, (const Cd*)C,
-                       (Cd*)V, w, (Cd*)Wf, F, status);
-    ASSX_LAUNCH_CHECK(ctx, "pca_basis_kernel");
-    return 0;
+  return launch_for_channels(ctx, "assx_pca_basis", "pca_basis_kernel", M, [&](auto mt) {
+    hipLaunchKernelGGL((pca_basis_kernel<decltype(mt)::value>), dim3(nblocks(F, WAVE)), dim3(WAVE), 0, (hipStream_t)stream,
+                       (const Cd*)C, (Cd*)V, w, (Cd*)Wf, F, status);
   });
 }
 

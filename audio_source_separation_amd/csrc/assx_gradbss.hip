@@ -20,20 +20,18 @@
 //   close      gb_loss_close_kernel: the data partials and the log-determinants in a fixed order
 //   solver     gb_corr_kernel per bin, gb_order_kernel (rank counting), gb_perm_kernel (one persistent workgroup)
 //
-// Every sum has a fixed order (assx_factor_common.hpp) and there is no float atomic: two runs give the same bits, and
+// Every sum has a fixed order (assx_perbin_common.hpp) and there is no float atomic: two runs give the same bits, and
 // assx_gradbss_iterate enqueues the kernels of the single entry points, so it gives their bits.  Every value that both the
 // loop and a single entry point produce comes out of the same kernel instantiation (the loss-only sweep is the moment
 // kernel with its accumulation switched off by an argument; ln|det W| always comes from the tail of gb_finalize_kernel).
-#include "assx_common.hpp"
-#include "assx_small_linalg.hpp"
-#include "assx_factor_common.hpp"
+#include "assx_perbin_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
+using namespace assx::pb;
 
 namespace {
 
-constexpr int GB_NW = BLK / WAVE;                    // waves of a moment / solver workgroup
 constexpr int GB_CHUNK = ASSX_GRADBSS_FRAME_CHUNK;   // frames of a moment workgroup
 constexpr int GB_FS = 64;                            // bin slices of the IVA weight pass, at most
 constexpr int MODE_LOGDET = 0, MODE_GRAD = 1, MODE_NAT = 2;
@@ -41,14 +39,8 @@ constexpr int GB_SOLVER_BINS = 1 << 16;              // the solver ranks the bin
 
 static_assert(GB_CHUNK % BLK == 0, "a chunk is whole trips of the workgroup");
 
-inline bool gb_in_envelope(int M, int F, int T) {
-  if (M < 2 || M > 8 || F < 1 || T < 1) return false;
-  if (F >= (1 << 28) || T >= (1 << 28)) return false;
-  return (long long)M * F * T < (1LL << 28);  // X stays below 4 GiB; no product below overflows
-}
-
-inline int gb_chunks(int T) { return (T + GB_CHUNK - 1) / GB_CHUNK; }
-inline int gb_slices(int F) { return F < GB_FS ? F : GB_FS; }
+inline int gb_chunks(int T) { return chunks(T, GB_CHUNK); }
+inline int gb_slices(int F) { return slices(F, GB_FS); }
 
 struct GbLayout {
   size_t part, lpart, logdet, r, r2p, corr, crit, pbuf, total;
@@ -76,24 +68,6 @@ GbLayout gb_layout(int M, int F, int T) {
   return L;
 }
 
-// rows of the cross-moment per wave: all M up to M = 6; at M = 7, 8 two wave pairs take half the rows each, so that a
-// lane holds at most 4 x 8 complex accumulators (128 VGPRs) instead of 8 x 8
-template <int M>
-struct RowSplit {
-  static constexpr int RG = M >= 7 ? 2 : 1;        // row groups
-  static constexpr int RPW = (M + RG - 1) / RG;    // rows per wave
-  static constexpr int NFG = GB_NW / RG;           // frame groups (waves that share a row group)
-};
-
-// a zero the optimiser cannot see through (no instruction is emitted): an LDS address formed with it is loop-variant
-__device__ __forceinline__ unsigned lds_opaque() {
-  unsigned v = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v));
-#endif
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // IVA weights: r2p[s,n,t] = sum over the bins of slice s of |y[n,f,t]|^2, one lane per frame, bins in ascending order
 // ---------------------------------------------------------------------------------------------------------------
@@ -102,15 +76,15 @@ __global__ void __launch_bounds__(WAVE) gb_weight_kernel(const Cd* __restrict__ 
                                                          double* __restrict__ r2p, int F, int T, int FS) {
   const int t = blockIdx.x * WAVE + threadIdx.x, s = blockIdx.y;
   if (t >= T) return;
-  const int f0 = (int)((long long)F * s / FS), f1 = (int)((long long)F * (s + 1) / FS);
+  int f0, f1;
+  slice_bounds(F, s, FS, f0, f1);
   double acc[M];
 #pragma unroll
   for (int n = 0; n < M; ++n) acc[n] = 0.0;
   for (int f = f0; f < f1; ++f) {
     const Cd* Wf = W + (size_t)f * M * M;
     Cd x[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+    load_frame<M>(X, f, t, F, T, x);
 #pragma unroll
     for (int n = 0; n < M; ++n) {
       Cd y = cmake<double>(0.0, 0.0);
@@ -130,9 +104,7 @@ __global__ void __launch_bounds__(BLK) gb_weight_sum_kernel(const double* __rest
   const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
   double v = 0.0;
   if (i < NT) {
-    double s = 0.0;
-    for (int k = 0; k < FS; ++k) s += r2p[(size_t)k * NT + i];
-    v = sqrt(s);
+    v = sqrt(slice_sum(r2p + i, NT, FS));
     r[i] = v;
   }
   const double tot = block_sum<double, BLK / WAVE>(v, red);
@@ -148,15 +120,14 @@ __global__ void __launch_bounds__(BLK) gb_moment_kernel(const Cd* __restrict__ X
                                                         const double* __restrict__ r, double eps, Cd* __restrict__ part,
                                                         double* __restrict__ lpart, int do_moment, int F, int T, int C) {
   using RS = RowSplit<M>;
-  constexpr int RG = RS::RG, RPW = RS::RPW, NFG = RS::NFG, ROWS = RG * RPW;
-  __shared__ Cd Ws[ROWS * M];  // rows past M are zero: a wave's spare row accumulates nothing
-  __shared__ double red[GB_NW][RPW * M * 2];
-  __shared__ double lred[GB_NW];
+  constexpr int RG = RS::RG, RPW = RS::RPW, NFG = RS::NFG;
+  __shared__ Cd Ws[RS::ROWS * M];  // rows past M are zero: a wave's spare row accumulates nothing
+  __shared__ double red[NW][RPW * M * 2];
+  __shared__ double lred[NW];
   // a flat grid of F C workgroups: neither count fits a grid's y dimension at every size of the envelope
   const int f = blockIdx.x / C, c = blockIdx.x % C, tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
   const int rg = wave % RG, fg = wave / RG, r0 = rg * RPW;
-  for (int i = tid; i < ROWS * M; i += BLK) Ws[i] = i < M * M ? W[(size_t)f * M * M + i] : cmake<double>(0.0, 0.0);
-  __syncthreads();
+  bin_matrix_to_lds<M>(Ws, W + (size_t)f * M * M);
 
   Cd acc[RPW][M];
 #pragma unroll
@@ -164,11 +135,10 @@ __global__ void __launch_bounds__(BLK) gb_moment_kernel(const Cd* __restrict__ X
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[i][m] = cmake<double>(0.0, 0.0);
   double lsum = 0.0;
-  const int t_end = T - c * GB_CHUNK < GB_CHUNK ? T : (c + 1) * GB_CHUNK;
+  const int t_end = chunk_end(c, GB_CHUNK, T);
   for (int t = c * GB_CHUNK + fg * WAVE + lane; t < t_end; t += NFG * WAVE) {
     Cd x[M], z[M], yr[RPW];
-#pragma unroll
-    for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+    load_frame<M>(X, f, t, F, T, x);
     const Cd* Wl = Ws;
     if constexpr (RG > 1) Wl = Ws + lds_opaque();  // W stays in LDS: hoisted out of the loop it would take 256 VGPRs at M = 8
 #pragma unroll
@@ -213,24 +183,9 @@ __global__ void __launch_bounds__(BLK) gb_moment_kernel(const Cd* __restrict__ X
     }
   }
 
-  if (do_moment) {
-#pragma unroll
-    for (int i = 0; i < RPW; ++i)
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        const double vr = wave_sum_down(acc[i][m].x), vi = wave_sum_down(acc[i][m].y);
-        if (lane == 0) red[wave][(i * M + m) * 2] = vr, red[wave][(i * M + m) * 2 + 1] = vi;
-      }
-    __syncthreads();
-    if (tid < M * M) {  // the frame groups of the entry's row group, in index order
-      const int n = tid / M, m = tid % M, g = n / RPW, i = n % RPW;
-      double sr = red[g][(i * M + m) * 2], si = red[g][(i * M + m) * 2 + 1];
-      for (int q = 1; q < NFG; ++q) sr += red[q * RG + g][(i * M + m) * 2], si += red[q * RG + g][(i * M + m) * 2 + 1];
-      part[((size_t)f * C + c) * M * M + tid] = cmake<double>(sr, si);
-    }
-  }
+  if (do_moment) reduce_rows_store<M>(acc, red, part + ((size_t)f * C + c) * M * M);
   if constexpr (MODEL == ASSX_GRADBSS_FDICA) {
-    const double tot = block_sum<double, GB_NW>(lsum, lred);
+    const double tot = block_sum<double, NW>(lsum, lred);
     if (tid == 0 && lpart) lpart[(size_t)f * C + c] = tot;
   }
 }
@@ -250,12 +205,8 @@ __global__ void __launch_bounds__(WAVE) gb_finalize_kernel(Cd* __restrict__ W, c
   if (active) {
     Ws[e] = W[(size_t)f * MM + e];
     if (mode != MODE_LOGDET) {
-      double gr = 0.0, gi = 0.0;
-      for (int c = 0; c < C; ++c) {
-        const Cd p = part[((size_t)f * C + c) * MM + e];
-        gr += p.x, gi += p.y;
-      }
-      Gs[e] = cmake<double>(gr / (double)T, gi / (double)T);
+      const Cd g = chunk_sum<MM>(part, f, C, e);
+      Gs[e] = cmake<double>(g.x / (double)T, g.y / (double)T);
     }
   }
   __syncthreads();
@@ -312,10 +263,9 @@ __global__ void __launch_bounds__(WAVE) gb_finalize_kernel(Cd* __restrict__ W, c
 __global__ void __launch_bounds__(BLK) gb_loss_close_kernel(const double* __restrict__ lpart, int n,
                                                             const double* __restrict__ logdet, int F, int T,
                                                             double* __restrict__ loss) {
-  __shared__ double red[BLK / WAVE];
-  const double data = strided_sum(lpart, n, 1, red);
-  __syncthreads();
-  const double ld = strided_sum(logdet, F, 1, red);
+  __shared__ double red[NW];
+  double data, ld;
+  loss_sums(lpart, n, logdet, F, red, data, ld);
   if (threadIdx.x == 0) loss[0] = 2.0 * data / (double)T - 2.0 * ld;
 }
 
@@ -327,8 +277,7 @@ template <int M>
 __device__ __forceinline__ void gb_presence(const Cd* __restrict__ X, const Cd* Ws, int f, int t, int F, int T, double eps,
                                             double (&P)[M]) {
   Cd x[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+  load_frame<M>(X, f, t, F, T, x);
   double tot = 0.0;
 #pragma unroll
   for (int n = 0; n < M; ++n) {
@@ -349,7 +298,7 @@ template <int M>
 __global__ void __launch_bounds__(BLK) gb_corr_kernel(const Cd* __restrict__ X, const Cd* __restrict__ W, double eps,
                                                       double* __restrict__ corr, int F, int T) {
   __shared__ Cd Ws[M * M];
-  __shared__ double red[GB_NW];
+  __shared__ double red[NW];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (tid < M * M) Ws[tid] = W[(size_t)f * M * M + tid];
   __syncthreads();
@@ -362,7 +311,7 @@ __global__ void __launch_bounds__(BLK) gb_corr_kernel(const Cd* __restrict__ X, 
     for (int n = 0; n < M; ++n) q += P[n];
     s += q * q;
   }
-  const double tot = block_sum<double, GB_NW>(s, red);
+  const double tot = block_sum<double, NW>(s, red);
   if (tid == 0) corr[f] = tot;
 }
 
@@ -420,7 +369,7 @@ __global__ void __launch_bounds__(BLK) gb_perm_kernel(const Cd* __restrict__ X, 
   constexpr int MM = M * M;
   constexpr int NPERM = M == 2 ? 2 : M == 3 ? 6 : M == 4 ? 24 : M == 5 ? 120 : M == 6 ? 720 : M == 7 ? 5040 : 40320;
   __shared__ Cd Ws[MM];
-  __shared__ double red[GB_NW][MM];
+  __shared__ double red[NW][MM];
   __shared__ double Cs[MM];
   __shared__ double bs[BLK];
   __shared__ int br[BLK];
@@ -498,19 +447,12 @@ __global__ void __launch_bounds__(BLK) gb_perm_kernel(const Cd* __restrict__ X, 
   }
 }
 
-static_assert(GB_NW == 4, "the solver adds four waves");
+static_assert(NW == 4, "the solver adds four waves");
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-int gb_check(assx_ctx* ctx, int M, int F, int T) {
-  ASSX_REQUIRE_CTX(ctx);
-  ASSX_REQUIRE(ctx, F >= 1 && T >= 1, ASSX_E_ARG, "invalid sizes F=%d T=%d", F, T);
-  ASSX_REQUIRE(ctx, M >= 2 && M <= 8, ASSX_E_UNSUPPORTED, "gradient IVA / FDICA: n_channels must be in [2, 8], got %d", M);
-  ASSX_REQUIRE(ctx, gb_in_envelope(M, F, T), ASSX_E_UNSUPPORTED,
-               "gradient IVA / FDICA: the input must stay below 4 GiB in complex128 (M*F*T < 2^28)");
-  return 0;
-}
+int gb_check(assx_ctx* ctx, int M, int F, int T) { return check_bin_sizes(ctx, "gradient IVA / FDICA", M, F, T); }
 
 int gb_check_model(assx_ctx* ctx, int model, int natural) {
   ASSX_REQUIRE(ctx, model == ASSX_GRADBSS_IVA || model == ASSX_GRADBSS_FDICA, ASSX_E_ARG, "model must be 0 (IVA) or 1 (FDICA), got %d",
@@ -519,16 +461,12 @@ int gb_check_model(assx_ctx* ctx, int model, int natural) {
   return 0;
 }
 
-struct GbRun {
+struct GbRun : RunBase {
   assx_ctx* ctx;
   const Cd* X;
   Cd* W;
-  char* ws;
   int M, F, T;
-  hipStream_t st;
   GbLayout L;
-  template <typename P>
-  P* at(size_t off) const { return (P*)(ws + off); }
 };
 
 // IVA: r of the current W and the data partials of its loss
@@ -549,14 +487,11 @@ int gb_stage_weights(const GbRun& g) {
 
 template <int MODEL, bool NATURAL>
 int gb_moment_launch(const GbRun& g, double eps, int do_moment) {
-  return dispatch_channels(g.ctx, "gradient IVA / FDICA", g.M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((gb_moment_kernel<MC, MODEL, NATURAL>), dim3((unsigned)g.F * gb_chunks(g.T)), dim3(BLK), 0, g.st, g.X,
-                       (const Cd*)g.W, (const double*)g.at<double>(g.L.r), eps, g.at<Cd>(g.L.part),
+  return launch_for_channels(g.ctx, "gradient IVA / FDICA", "gb_moment_kernel", g.M, [&](auto mt) {
+    hipLaunchKernelGGL((gb_moment_kernel<decltype(mt)::value, MODEL, NATURAL>), dim3((unsigned)g.F * gb_chunks(g.T)),
+                       dim3(BLK), 0, g.st, g.X, (const Cd*)g.W, (const double*)g.at<double>(g.L.r), eps, g.at<Cd>(g.L.part),
                        MODEL == ASSX_GRADBSS_FDICA ? g.at<double>(g.L.lpart) : (double*)nullptr, do_moment, g.F, g.T,
                        gb_chunks(g.T));
-    ASSX_LAUNCH_CHECK(g.ctx, "gb_moment_kernel");
-    return 0;
   });
 }
 
@@ -570,12 +505,9 @@ int gb_stage_moment(const GbRun& g, int model, int natural, double eps, int do_m
 }
 
 int gb_stage_finalize(const GbRun& g, int mode, double lr, int32_t* status) {
-  return dispatch_channels(g.ctx, "gradient IVA / FDICA", g.M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((gb_finalize_kernel<MC>), dim3(g.F), dim3(WAVE), 0, g.st, g.W, (const Cd*)g.at<Cd>(g.L.part),
-                       g.at<double>(g.L.logdet), mode, lr, gb_chunks(g.T), g.T, status);
-    ASSX_LAUNCH_CHECK(g.ctx, "gb_finalize_kernel");
-    return 0;
+  return launch_for_channels(g.ctx, "gradient IVA / FDICA", "gb_finalize_kernel", g.M, [&](auto mt) {
+    hipLaunchKernelGGL((gb_finalize_kernel<decltype(mt)::value>), dim3(g.F), dim3(WAVE), 0, g.st, g.W,
+                       (const Cd*)g.at<Cd>(g.L.part), g.at<double>(g.L.logdet), mode, lr, gb_chunks(g.T), g.T, status);
   });
 }
 
@@ -595,7 +527,7 @@ int gb_first_sweep(const GbRun& g, int model, int natural, double eps, int do_mo
 }
 
 GbRun gb_run(assx_ctx* ctx, const void* X, void* W, void* ws, int M, int F, int T, void* stream) {
-  return GbRun{ctx, (const Cd*)X, (Cd*)W, (char*)ws, M, F, T, (hipStream_t)stream, gb_layout(M, F, T)};
+  return GbRun{{(char*)ws, (hipStream_t)stream}, ctx, (const Cd*)X, (Cd*)W, M, F, T, gb_layout(M, F, T)};
 }
 
 }  // namespace
@@ -603,7 +535,7 @@ GbRun gb_run(assx_ctx* ctx, const void* X, void* W, void* ws, int M, int F, int 
 extern "C" {
 
 size_t assx_gradbss_workspace_bytes(int M, int F, int T) {
-  if (!gb_in_envelope(M, F, T)) return 0;
+  if (!in_envelope(M, F, T)) return 0;
   return gb_layout(M, F, T).total;
 }
 

@@ -19,27 +19,21 @@
 // The spatial update is assx_idlma_space_update on R with domain 2, the scale assx_projection_back_scale.
 //
 // Every sum has a fixed order and there is no float atomic: two runs give the same bits.
-#include "assx_common.hpp"
-#include "assx_small_linalg.hpp"
-#include "assx_factor_common.hpp"
+#include "assx_perbin_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
+using namespace assx::pb;
 
 namespace {
 
 constexpr int ID_VEC = 4;                         // frames of one thread: one 16-byte store of float32
 constexpr int ID_CHUNK = ASSX_IDLMA_FRAME_CHUNK;  // frames of one workgroup
-constexpr int ID_NW = BLK / WAVE;
 
 static_assert(ID_CHUNK == BLK * ID_VEC, "a chunk is one trip of the workgroup");
 
-inline bool id_in_envelope(int M, int F, int T) {
-  if (M < 2 || M > 8 || F < 1 || T < M || F >= (1 << 28) || T >= (1 << 28)) return false;
-  return (long long)M * F * T < (1LL << 28);  // every array stays below 4 GiB; no product below overflows
-}
-
-inline int id_chunks(int T) { return (T + ID_CHUNK - 1) / ID_CHUNK; }
+inline bool id_in_envelope(int M, int F, int T) { return in_envelope(M, F, T, M); }  // at least M frames
+inline int id_chunks(int T) { return chunks(T, ID_CHUNK); }
 
 // part (F, chunks) loss partials, ldet (F), scale (N,F) complex, R (N,F,T), then the scratch of the spatial update and
 // the projection-back scale (assx_workspace_bytes)
@@ -90,7 +84,7 @@ __global__ void __launch_bounds__(BLK) idlma_tail_kernel(const Cd* __restrict__ 
                                                          const double* __restrict__ R, float* __restrict__ inp,
                                                          double* __restrict__ part, PowSpec ps, int F, int T, int CH,
                                                          int vec) {
-  __shared__ double red[ID_NW];
+  __shared__ double red[NW];
   const int f = blockIdx.x / CH, ch = blockIdx.x % CH;
   const int t0 = ch * ID_CHUNK + (int)threadIdx.x * ID_VEC;
   const Cd* Wb = W + (size_t)f * M * M;
@@ -100,7 +94,7 @@ __global__ void __launch_bounds__(BLK) idlma_tail_kernel(const Cd* __restrict__ 
   for (int k = 0; k < ID_VEC; ++k) {
     const int t = t0 + k;
     if (t < T) {
-      Cd x[M];
+      Cd x[M];  // not load_frame of assx_perbin_common.hpp: inside this unrolled loop it moves the registers of every instance
 #pragma unroll
       for (int m = 0; m < M; ++m) x[m] = tocx(ldv(X + ((size_t)m * F + f) * T + t));
 #pragma unroll
@@ -134,7 +128,7 @@ __global__ void __launch_bounds__(BLK) idlma_tail_kernel(const Cd* __restrict__ 
     }
   }
   if constexpr (LOSS) {
-    const double tot = block_sum<double, ID_NW>(acc, red);
+    const double tot = block_sum<double, NW>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
   }
 }
@@ -157,10 +151,9 @@ __global__ void __launch_bounds__(WAVE) idlma_logdet_kernel(const Cd* __restrict
 __global__ void __launch_bounds__(BLK) idlma_loss_close_kernel(const double* __restrict__ part, int n,
                                                                const double* __restrict__ ldet, int F, int T,
                                                                double* __restrict__ loss) {
-  __shared__ double red[BLK / WAVE];
-  const double data = strided_sum(part, n, 1, red);
-  __syncthreads();
-  const double ld = strided_sum(ldet, F, 1, red);
+  __shared__ double red[NW];
+  double data, ld;
+  loss_sums(part, n, ldet, F, red, data, ld);
   if (threadIdx.x == 0) loss[0] = data - 2.0 * (double)T * ld;
 }
 

@@ -27,16 +27,14 @@
 // and a single entry point produce comes out of the same kernel instantiation through explicit fused multiply-adds, so
 // assx_pdsbss_iterate gives the bits of update + loss called in turn although it skips the adjoint sweep that
 // assx_pdsbss_update has to begin with (the partials of the previous sweep 2 are those very numbers).
-#include "assx_common.hpp"
-#include "assx_small_linalg.hpp"
-#include "assx_factor_common.hpp"
+#include "assx_perbin_common.hpp"
 
 using namespace assx;
 using namespace assx::mf;
+using namespace assx::pb;
 
 namespace {
 
-constexpr int PD_NW = BLK / WAVE;                  // waves of a sweep-2 workgroup
 constexpr int PD_CHUNK = ASSX_PDSBSS_FRAME_CHUNK;  // frames of a sweep-2 workgroup
 constexpr int PD_FS = 64;                          // bin slices of sweep 1, at most
 constexpr int PD_SWEEPS = 40;                      // Jacobi sweeps, at most (a full-rank 8 x 8 takes 6 to 9)
@@ -46,16 +44,9 @@ enum { FIN_LOGDET = 0, FIN_UPDATE = 1, FIN_PROX = 2, FIN_ADJOINT = 3, FIN_GRAM =
 enum { SHRINK_NONE = 0, SHRINK_STEP = 1, SHRINK_PROX = 2 };
 
 static_assert(PD_CHUNK % BLK == 0, "a chunk is whole trips of the workgroup");
-static_assert(PD_NW == 4, "the row split pairs four waves");
 
-inline bool pd_in_envelope(int M, int F, int T) {
-  if (M < 2 || M > 8 || F < 1 || T < 1) return false;
-  if (F >= (1 << 28) || T >= (1 << 28)) return false;
-  return (long long)M * F * T < (1LL << 28);  // X stays below 4 GiB; no product below overflows
-}
-
-inline int pd_chunks(int T) { return (T + PD_CHUNK - 1) / PD_CHUNK; }
-inline int pd_slices(int F) { return F < PD_FS ? F : PD_FS; }
+inline int pd_chunks(int T) { return chunks(T, PD_CHUNK); }
+inline int pd_slices(int F) { return slices(F, PD_FS); }
 
 // part: partials of G (F,C,M,M) complex; D (F,M,M) complex; logdet (F), also the largest eigenvalue of a bin's Gram matrix;
 // r2z, r2w (FS,M,T): slice partials of sum_f |z|^2 and sum_f |W x|^2; s (M,T): the shrink factor; lpart: block partials
@@ -82,24 +73,6 @@ PdLayout pd_layout(int M, int F, int T) {
   return L;
 }
 
-// rows of G per wave: all M up to M = 6; at M = 7, 8 two wave pairs take half the rows each, so that a lane holds at most
-// 4 x 8 complex accumulators (128 VGPRs) instead of 8 x 8
-template <int M>
-struct PdRowSplit {
-  static constexpr int RG = M >= 7 ? 2 : 1;
-  static constexpr int RPW = (M + RG - 1) / RG;
-  static constexpr int NFG = PD_NW / RG;
-};
-
-// a zero the optimiser cannot see through (no instruction is emitted): an LDS address formed with it is loop-variant
-__device__ __forceinline__ unsigned pd_lds_opaque() {
-  unsigned v = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("" : "+v"(v));
-#endif
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Sweep 1: r2z[sl,n,t] = sum over the bins of slice sl of |z[f,n,t]|^2 (do_z) and r2w the same of |(W x)[n]|^2 (do_w),
 // one lane per frame, bins ascending.  D and W are read through wave-uniform addresses.
@@ -111,15 +84,15 @@ __global__ void __launch_bounds__(WAVE) pd_group_kernel(const Cd* __restrict__ X
                                                         double* __restrict__ r2w, int do_z, int do_w, int F, int T, int FS) {
   const int t = blockIdx.x * WAVE + threadIdx.x, sl = blockIdx.y;
   if (t >= T) return;
-  const int f0 = (int)((long long)F * sl / FS), f1 = (int)((long long)F * (sl + 1) / FS);
+  int f0, f1;
+  slice_bounds(F, sl, FS, f0, f1);
   const double rn = do_z ? 1.0 / norm[0] : 0.0;
   double az[M], aw[M];
 #pragma unroll
   for (int n = 0; n < M; ++n) az[n] = 0.0, aw[n] = 0.0;
   for (int f = f0; f < f1; ++f) {
     Cd x[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+    load_frame<M>(X, f, t, F, T, x);
     if (do_z) {
       const Cd* Df = D + (size_t)f * M * M;
 #pragma unroll
@@ -158,7 +131,8 @@ __global__ void __launch_bounds__(BLK) pd_norm2_kernel(const Cd* __restrict__ z,
   const size_t i = (size_t)blockIdx.x * BLK + threadIdx.x;
   const int sl = blockIdx.y;
   if (i >= NT) return;
-  const int f0 = (int)((long long)F * sl / FS), f1 = (int)((long long)F * (sl + 1) / FS);
+  int f0, f1;
+  slice_bounds(F, sl, FS, f0, f1);
   double a = 0.0;
   for (int f = f0; f < f1; ++f) {
     const Cd v = z[(size_t)f * NT + i];
@@ -179,19 +153,13 @@ __global__ void __launch_bounds__(BLK) pd_shrink_kernel(const double* __restrict
   double v = 0.0;
   if (i < NT) {
     if (do_z != SHRINK_NONE) {
-      double a = 0.0;
-      for (int k = 0; k < FS; ++k) a += r2z[(size_t)k * NT + i];
-      double den = sqrt(a);
+      double den = sqrt(slice_sum(r2z + i, NT, FS));
       if (den <= 0.0) den = imu;
       const double q = 1.0 - imu / den;
       const double p = Creg * (q > 0.0 ? q : 0.0);
       s_out[i] = do_z == SHRINK_STEP ? 1.0 - p : p;
     }
-    if (do_w) {
-      double a = 0.0;
-      for (int k = 0; k < FS; ++k) a += r2w[(size_t)k * NT + i];
-      v = sqrt(a);
-    }
+    if (do_w) v = sqrt(slice_sum(r2w + i, NT, FS));
   }
   if (do_w) {
     const double tot = block_sum<double, BLK / WAVE>(v, red);
@@ -219,8 +187,7 @@ __global__ void __launch_bounds__(WAVE) pd_forward_kernel(const Cd* __restrict__
   const double rn = 1.0 / norm[0];
   const Cd* Df = D + (size_t)f * M * M;
   Cd x[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+  load_frame<M>(X, f, t, F, T, x);
 #pragma unroll
   for (int n = 0; n < M; ++n) {
     const Cd yv = y[((size_t)f * M + n) * T + t];
@@ -242,16 +209,14 @@ __global__ void __launch_bounds__(BLK) pd_dual_kernel(const Cd* __restrict__ X, 
                                                       const Cd* __restrict__ D, const double* __restrict__ s,
                                                       const double* __restrict__ norm, double alpha, Cd* __restrict__ part,
                                                       int do_update, int F, int T, int C) {
-  using RS = PdRowSplit<M>;
-  constexpr int RG = RS::RG, RPW = RS::RPW, NFG = RS::NFG, ROWS = RG * RPW;
-  __shared__ Cd Ds[ROWS * M];  // rows past M are zero and never used
-  __shared__ double red[PD_NW][RPW * M * 2];
+  using RS = RowSplit<M>;
+  constexpr int RG = RS::RG, RPW = RS::RPW, NFG = RS::NFG;
+  __shared__ Cd Ds[RS::ROWS * M];  // rows past M are zero and never used
+  __shared__ double red[NW][RPW * M * 2];
   // a flat grid of F C workgroups: neither count fits a grid's y dimension at every size of the envelope
   const int f = blockIdx.x / C, c = blockIdx.x % C, tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
   const int rg = wave % RG, fg = wave / RG, r0 = rg * RPW;
-  for (int i = tid; i < ROWS * M; i += BLK)
-    Ds[i] = (do_update && i < M * M) ? D[(size_t)f * M * M + i] : cmake<double>(0.0, 0.0);
-  __syncthreads();
+  bin_matrix_to_lds<M>(Ds, D + (size_t)f * M * M, !do_update);
   const double rn = do_update ? 1.0 / norm[0] : 0.0;
   const double beta = 1.0 - alpha;
 
@@ -260,13 +225,12 @@ __global__ void __launch_bounds__(BLK) pd_dual_kernel(const Cd* __restrict__ X, 
   for (int i = 0; i < RPW; ++i)
 #pragma unroll
     for (int m = 0; m < M; ++m) acc[i][m] = cmake<double>(0.0, 0.0);
-  const int t_end = T - c * PD_CHUNK < PD_CHUNK ? T : (c + 1) * PD_CHUNK;
+  const int t_end = chunk_end(c, PD_CHUNK, T);
   for (int t = c * PD_CHUNK + fg * WAVE + lane; t < t_end; t += NFG * WAVE) {
     Cd x[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) x[m] = X[((size_t)m * F + f) * T + t];
+    load_frame<M>(X, f, t, F, T, x);
     const Cd* Dl = Ds;
-    if constexpr (RG > 1) Dl = Ds + pd_lds_opaque();  // D stays in LDS: hoisted out of the loop it would take 128 VGPRs more
+    if constexpr (RG > 1) Dl = Ds + lds_opaque();  // D stays in LDS: hoisted out of the loop it would take 128 VGPRs more
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
       const int n = r0 + i;
@@ -293,20 +257,7 @@ __global__ void __launch_bounds__(BLK) pd_dual_kernel(const Cd* __restrict__ X, 
     }
   }
 
-#pragma unroll
-  for (int i = 0; i < RPW; ++i)
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      const double vr = wave_sum_down(acc[i][m].x), vi = wave_sum_down(acc[i][m].y);
-      if (lane == 0) red[wave][(i * M + m) * 2] = vr, red[wave][(i * M + m) * 2 + 1] = vi;
-    }
-  __syncthreads();
-  if (tid < M * M) {  // the frame groups of the entry's row group, in index order
-    const int n = tid / M, m = tid % M, g = n / RPW, i = n % RPW;
-    double sr = red[g][(i * M + m) * 2], si = red[g][(i * M + m) * 2 + 1];
-    for (int q = 1; q < NFG; ++q) sr += red[q * RG + g][(i * M + m) * 2], si += red[q * RG + g][(i * M + m) * 2 + 1];
-    part[((size_t)f * C + c) * M * M + tid] = cmake<double>(sr, si);
-  }
+  reduce_rows_store<M>(acc, red, part + ((size_t)f * C + c) * M * M);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -338,10 +289,7 @@ __global__ void __launch_bounds__(WAVE) pd_finalize_kernel(Cd* __restrict__ W, c
     if (active) {
       Cd g = cmake<double>(0.0, 0.0);
       if (mode == FIN_UPDATE || mode == FIN_ADJOINT || mode == FIN_GRAM) {
-        for (int c = 0; c < C; ++c) {
-          const Cd p = part[((size_t)f * C + c) * MM + e];
-          g.x += p.x, g.y += p.y;
-        }
+        g = chunk_sum<MM>(part, f, C, e);
         if (mode != FIN_GRAM) {
           const double rn = 1.0 / norm[0];
           g = cmake<double>(g.x * rn, g.y * rn);
@@ -550,10 +498,9 @@ __global__ void __launch_bounds__(BLK) pd_norm_max_kernel(const double* __restri
 __global__ void __launch_bounds__(BLK) pd_loss_close_kernel(const double* __restrict__ lpart, int n,
                                                             const double* __restrict__ logdet, int F, double Creg,
                                                             double* __restrict__ loss, double* __restrict__ terms) {
-  __shared__ double red[BLK / WAVE];
-  const double data = strided_sum(lpart, n, 1, red);
-  __syncthreads();
-  const double ld = strided_sum(logdet, F, 1, red);
+  __shared__ double red[NW];
+  double data, ld;
+  loss_sums(lpart, n, logdet, F, red, data, ld);
   if (threadIdx.x == 0) {
     const double pen = Creg * data;
     loss[0] = pen - ld;
@@ -564,14 +511,7 @@ __global__ void __launch_bounds__(BLK) pd_loss_close_kernel(const double* __rest
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-int pd_check(assx_ctx* ctx, int M, int F, int T) {
-  ASSX_REQUIRE_CTX(ctx);
-  ASSX_REQUIRE(ctx, F >= 1 && T >= 1, ASSX_E_ARG, "invalid sizes F=%d T=%d", F, T);
-  ASSX_REQUIRE(ctx, M >= 2 && M <= 8, ASSX_E_UNSUPPORTED, "ProxLaplaceIVA: n_channels must be in [2, 8], got %d", M);
-  ASSX_REQUIRE(ctx, pd_in_envelope(M, F, T), ASSX_E_UNSUPPORTED,
-               "ProxLaplaceIVA: the input must stay below 4 GiB in complex128 (M*F*T < 2^28)");
-  return 0;
-}
+int pd_check(assx_ctx* ctx, int M, int F, int T) { return check_bin_sizes(ctx, "ProxLaplaceIVA", M, F, T); }
 
 int pd_check_penalty(assx_ctx* ctx, int penalty) {
   ASSX_REQUIRE(ctx, penalty == ASSX_PDSBSS_LAPLACE, ASSX_E_ARG, "penalty must be 0 (the Laplace group norm), got %d", penalty);
@@ -585,42 +525,32 @@ int pd_check_steps(assx_ctx* ctx, double Creg, double mu1, double mu2, double al
   return 0;
 }
 
-struct PdRun {
+struct PdRun : RunBase {
   assx_ctx* ctx;
   const Cd* X;
   Cd* W;
   Cd* y;
   const double* norm;
-  char* ws;
   int M, F, T;
-  hipStream_t st;
   PdLayout L;
-  template <typename P>
-  P* at(size_t off) const { return (P*)(ws + off); }
 };
 
 // sweep 2, or with do_update = 0 the adjoint partials of y as it stands
 int pd_stage_dual(const PdRun& g, Cd* y, size_t ysF, size_t ysN, double alpha, int do_update) {
-  return dispatch_channels(g.ctx, "ProxLaplaceIVA", g.M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((pd_dual_kernel<MC>), dim3((unsigned)g.F * pd_chunks(g.T)), dim3(BLK), 0, g.st, g.X, y, ysF, ysN,
-                       (const Cd*)g.at<Cd>(g.L.D), (const double*)g.at<double>(g.L.s), g.norm, alpha, g.at<Cd>(g.L.part),
-                       do_update, g.F, g.T, pd_chunks(g.T));
-    ASSX_LAUNCH_CHECK(g.ctx, "pd_dual_kernel");
-    return 0;
+  return launch_for_channels(g.ctx, "ProxLaplaceIVA", "pd_dual_kernel", g.M, [&](auto mt) {
+    hipLaunchKernelGGL((pd_dual_kernel<decltype(mt)::value>), dim3((unsigned)g.F * pd_chunks(g.T)), dim3(BLK), 0, g.st, g.X,
+                       y, ysF, ysN, (const Cd*)g.at<Cd>(g.L.D), (const double*)g.at<double>(g.L.s), g.norm, alpha,
+                       g.at<Cd>(g.L.part), do_update, g.F, g.T, pd_chunks(g.T));
   });
 }
 
 int pd_stage_finalize(const PdRun& g, int F, int mode, const Cd* in, Cd* out, double mu, double mu12, double alpha,
                       int32_t* status) {
-  return dispatch_channels(g.ctx, "ProxLaplaceIVA", g.M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((pd_finalize_kernel<MC>), dim3(F), dim3(WAVE), 0, g.st, g.W, in, out,
+  return launch_for_channels(g.ctx, "ProxLaplaceIVA", "pd_finalize_kernel", g.M, [&](auto mt) {
+    hipLaunchKernelGGL((pd_finalize_kernel<decltype(mt)::value>), dim3(F), dim3(WAVE), 0, g.st, g.W, in, out,
                        g.ws ? (const Cd*)g.at<Cd>(g.L.part) : (const Cd*)nullptr, g.ws ? g.at<Cd>(g.L.D) : (Cd*)nullptr,
                        g.ws ? g.at<double>(g.L.logdet) : (double*)nullptr, g.norm, mode, mu, mu12, alpha, pd_chunks(g.T),
                        status);
-    ASSX_LAUNCH_CHECK(g.ctx, "pd_finalize_kernel");
-    return 0;
   });
 }
 
@@ -666,7 +596,7 @@ int pd_iteration(const PdRun& g, double Creg, double mu1, double mu2, double alp
 }
 
 PdRun pd_run(assx_ctx* ctx, const void* X, const void* norm, void* W, void* y, void* ws, int M, int F, int T, void* stream) {
-  return PdRun{ctx, (const Cd*)X, (Cd*)W, (Cd*)y, (const double*)norm, (char*)ws, M, F, T, (hipStream_t)stream,
+  return PdRun{{(char*)ws, (hipStream_t)stream}, ctx, (const Cd*)X, (Cd*)W, (Cd*)y, (const double*)norm, M, F, T,
                pd_layout(M, F, T)};
 }
 
@@ -675,7 +605,7 @@ PdRun pd_run(assx_ctx* ctx, const void* X, const void* norm, void* W, void* y, v
 extern "C" {
 
 size_t assx_pdsbss_workspace_bytes(int M, int F, int T) {
-  if (!pd_in_envelope(M, F, T)) return 0;
+  if (!in_envelope(M, F, T)) return 0;
   return pd_layout(M, F, T).total;
 }
 
@@ -721,12 +651,9 @@ int assx_pdsbss_forward(assx_ctx* ctx, const void* X, const double* norm, const 
   if (rc) return rc;
   ASSX_REQUIRE(ctx, X && norm && y && D && z, ASSX_E_NULL, "assx_pdsbss_forward: NULL array");
   const int ntile = (int)nblocks(T, WAVE);
-  return dispatch_channels(ctx, "ProxLaplaceIVA", M, [&](auto mt) -> int {
-    constexpr int MC = decltype(mt)::value;
-    hipLaunchKernelGGL((pd_forward_kernel<MC>), dim3((unsigned)F * ntile), dim3(WAVE), 0, (hipStream_t)stream, (const Cd*)X,
-                       (const Cd*)y, (const Cd*)D, norm, (Cd*)z, F, T, ntile);
-    ASSX_LAUNCH_CHECK(ctx, "pd_forward_kernel");
-    return 0;
+  return launch_for_channels(ctx, "ProxLaplaceIVA", "pd_forward_kernel", M, [&](auto mt) {
+    hipLaunchKernelGGL((pd_forward_kernel<decltype(mt)::value>), dim3((unsigned)F * ntile), dim3(WAVE), 0,
+                       (hipStream_t)stream, (const Cd*)X, (const Cd*)y, (const Cd*)D, norm, (Cd*)z, F, T, ntile);
   });
 }
 

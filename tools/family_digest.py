@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""SHA-256 of everything the entry points of the seven factorisation families write, for A/B runs of two builds of the
-library.
+"""SHA-256 of everything the entry points of the seven factorisation families and of the four per-bin BSS families
+write, for A/B runs of two builds of the library.
 
     ASSX_LIB_PATH=/path/to/other/libassx.so python tools/family_digest.py > a.txt
     python tools/family_digest.py > b.txt && diff a.txt b.txt
+
+`python tools/family_digest.py factorisations` or `... perbin` prints one of the two groups alone; the lines of a group
+do not depend on whether the other runs.
 
 One line `case entry sha256` per output array.  No tolerance and no reference: every family promises fixed-order sums,
 so two builds that compute the same sums print the same lines.  Every `Engine.*` entry point of a family is called once
@@ -22,10 +25,19 @@ from a seeded state; `*_iterate` runs with the loss on.  The states are the ones
                   branch); every case of `SIZE_CASES` of tests/test_gpu_ipsdta.py and tests/test_gpu_tipsdta.py from the
                   test's seeded start; the spatial update and `*_iterate` (2 iterations) run 2 sweeps, and none where
                   there are fewer frames than channels, as in the tests
+  gradient BSS    every case of `gradbss_envelope_np.GRID`: update and iterate of the four classes, both losses and
+                  FDICA's permutation solver; 2 iterations
+  ProxLaplaceIVA  every case of `pdsbss_envelope_np.GRID`: operator norm, adjoint, forward, both proxes, update, loss
+                  and iterate; 2 iterations
+  beamformers     every case of `beamform_envelope_np.GRID`: the calls of tests/test_gpu_beamform_envelope.py (`bf_*`,
+                  `pca_basis`, `mdp_scale`)
+  GaussIDLMA      the sizes and options of `idlma_np.CASES` from a seeded W and network output: the single entry points
+                  and `idlma_step` twice, the network's next input fed back as its output
 
 Between them the cases cross every boundary of a fixed-order sum: more than 64 frames and not a multiple of 64, 17 bases
 (a second chunk of 16), 9 or more bins (a second slab), and for the MNMFs 130 frames (three spatial slices, more than
-one evaluation workgroup).
+one evaluation workgroup); for the per-bin families the row split between 6 and 7 channels, a second frame chunk, a
+partial last wave of frames and more than one bin slice.
 """
 import hashlib
 import os
@@ -40,8 +52,13 @@ import torch  # noqa: E402
 
 import cnmf_np as cn  # noqa: E402
 import covnmf_envelope_np as cvenv  # noqa: E402
+import beamform_envelope_np as benv  # noqa: E402
 import envelope_np as env  # noqa: E402
+import gradbss_envelope_np as genv  # noqa: E402
+import gradbss_np as gb  # noqa: E402
+import idlma_np as idl  # noqa: E402
 import ipsdta_np as ip  # noqa: E402
+import pdsbss_envelope_np as penv  # noqa: E402
 import ntf_np as nt  # noqa: E402
 import psdtf_np as pt  # noqa: E402
 from test_gpu_cnmf import EDGES as CNMF_CASES  # noqa: E402
@@ -49,6 +66,7 @@ from test_gpu_ipsdta import SIZE_CASES as GAUSS_CASES  # noqa: E402
 from test_gpu_ntf import ENVELOPE as NTF_CASES  # noqa: E402
 from test_gpu_psdtf import SIZES as PSD_SIZES  # noqa: E402
 from test_gpu_tipsdta import SIZE_CASES as T_CASES  # noqa: E402
+from audio_source_separation_amd import _lib  # noqa: E402
 from audio_source_separation_amd.ops import Engine  # noqa: E402
 
 ITERATIONS = 3       # MNMF and FastMNMF
@@ -303,7 +321,113 @@ def ipsdta(eng, case):
         line(tag, "%siterate.%s" % (pre, name), t)
 
 
-def main():
+def dev(eng, a):
+    return torch.as_tensor(np.ascontiguousarray(a), device=eng.dev)
+
+
+def gradbss(eng, case):
+    M, F, T, seed = genv.GRID[case]
+    X, W = genv.state(M, F, T, seed)
+    Xd, ws = dev(eng, X), eng.gradbss_workspace(M, F, T)
+    code = {"iva": _lib.GRADBSS_IVA, "fdica": _lib.GRADBSS_FDICA}
+    for cls, (model, natural) in gb.CLASSES.items():
+        Wd, status = dev(eng, W), eng.new_status(1)
+        eng.gradbss_update(code[model], natural, Xd, Wd, ws, status=status)
+        line(case, "gradbss_update.%s.W" % cls, Wd)
+        line(case, "gradbss_update.%s.status" % cls, status)
+        Wd, status, loss = dev(eng, W), eng.new_status(1), eng.empty((SHORT + 1,), dtype=torch.float64)
+        eng.gradbss_iterate(SHORT, code[model], natural, Xd, Wd, ws, loss=loss, status=status)
+        for name, t in (("W", Wd), ("loss", loss), ("status", status)):
+            line(case, "gradbss_iterate.%s.%s" % (cls, name), t)
+    for model in gb.MODELS:
+        line(case, "gradbss_loss." + model, eng.gradbss_loss(code[model], Xd, dev(eng, W), ws))
+    Wd = dev(eng, W)
+    order, perm = eng.fdica_solve_permutation(Xd, Wd, ws)
+    for name, t in (("order", order), ("perm", perm), ("W", Wd)):
+        line(case, "fdica_solve_permutation." + name, t)
+
+
+def pdsbss(eng, case):
+    X, W, y, norm, par = penv.state(*penv.GRID[case])
+    M, F, T = X.shape
+    Xd, ws, status = dev(eng, X), eng.pdsbss_workspace(M, F, T), eng.new_status(1)
+    nd = torch.tensor([norm], dtype=torch.float64, device=eng.dev)
+    line(case, "pdsbss_operator_norm", eng.pdsbss_operator_norm(Xd, ws, status=status))
+    line(case, "pdsbss_adjoint", eng.pdsbss_adjoint(Xd, nd, dev(eng, y), ws))
+    line(case, "pdsbss_forward", eng.pdsbss_forward(Xd, nd, dev(eng, y), dev(eng, W)))
+    line(case, "pdsbss_prox_logdet", eng.pdsbss_prox_logdet(dev(eng, W), par["mu1"], status=status))
+    line(case, "pdsbss_prox_group", eng.pdsbss_prox_group(dev(eng, y), ws, C=par["C"], mu=1 / par["mu2"]))
+    loss, terms = eng.empty((1,), dtype=torch.float64), eng.empty((2,), dtype=torch.float64)
+    eng.pdsbss_loss(Xd, dev(eng, W), ws, C=par["C"], loss=loss, terms=terms)
+    line(case, "pdsbss_loss", loss)
+    line(case, "pdsbss_loss.terms", terms)
+    Wd, yd = dev(eng, W), dev(eng, y)
+    eng.pdsbss_update(Xd, nd, Wd, yd, ws, status=status, **par)
+    line(case, "pdsbss_update.W", Wd)
+    line(case, "pdsbss_update.y", yd)
+    Wd, yd, loss = dev(eng, W), dev(eng, y), eng.empty((SHORT + 1,), dtype=torch.float64)
+    eng.pdsbss_iterate(SHORT, Xd, nd, Wd, yd, ws, loss=loss, status=status, **par)
+    for name, t in (("W", Wd), ("y", yd), ("loss", loss), ("status", status)):
+        line(case, "pdsbss_iterate." + name, t)
+
+
+def beamform(eng, case):
+    """The calls of tests/test_gpu_beamform_envelope.py's `run`."""
+    X, A, R, Ys, ref, eps = benv.state(*benv.GRID[case])
+    M, F, T = X.shape
+    Xd, Ad, Yd, status = dev(eng, X), dev(eng, A), dev(eng, Ys), eng.new_status(1)
+    Wf, s = eng.bf_ds_weights(Ad, ref)
+    for name, t in (("Wf", Wf), ("s", s)):
+        line(case, "bf_ds_weights." + name, t)
+    line(case, "bf_apply.ds", eng.bf_apply(Xd, Wf, s))
+    Wf, s = eng.bf_ml_weights(Ad, dev(eng, R), ref, eps, status)
+    for name, t in (("Wf", Wf), ("s", s)):
+        line(case, "bf_ml_weights." + name, t)
+    line(case, "bf_apply.ml", eng.bf_apply(Xd, Wf, s))
+    line(case, "mdp_scale", eng.mdp_scale(Yd, Xd))
+    line(case, "mdp_scale.one_channel", eng.mdp_scale(Yd, Xd[ref:ref + 1].contiguous()))
+    C = eng.cov_accumulate(Xd.unsqueeze(0)).reshape(F, M, M)
+    V, w, Wp = eng.pca_basis(C, status)
+    for name, t in (("V", V), ("w", w), ("Wf", Wp)):
+        line(case, "pca_basis." + name, t)
+    line(case, "bf_apply.pca", eng.bf_apply(Xd, Wp))
+    line(case, "beamform.status", status)
+
+
+def idlma(eng, case):
+    """The single entry points once, then idlma_step twice with the identity in the network's place."""
+    name, M, F, T, domain, _, seed, opt = case
+    rng = np.random.default_rng(5000 + seed)
+    X = idl.convolutive_mixture(M, F, T, seed)
+    W = np.eye(M) + 0.3 / np.sqrt(M) * env._cgauss(rng, (F, M, M))
+    raw = (0.05 + rng.random((M, F, T))).astype(np.float32)
+    flooring, ref = opt.get("dnn_flooring", 1e-5), opt.get("reference_id", 0)
+    Xd, ws = dev(eng, X), eng.idlma_workspace(M, F, T)
+    line(name, "idlma_dnn_input", eng.idlma_dnn_input(Xd, dev(eng, W), domain=domain))
+    d, R = eng.empty((M, F, T), dtype=torch.float32), eng.empty((M, F, T), dtype=torch.float64)
+    eng.idlma_variance(dev(eng, raw), d, R, domain=domain, dnn_flooring=flooring, eps=EPS)
+    line(name, "idlma_variance.dnn_output", d)
+    line(name, "idlma_variance.R", R)
+    line(name, "idlma_loss", eng.idlma_loss(Xd, dev(eng, W), R, ws))
+    Wd = dev(eng, W)
+    eng.idlma_normalize_pb(Wd, dev(eng, env._cgauss(rng, (M, F))))
+    line(name, "idlma_normalize_pb", Wd)
+    Wd, status = dev(eng, W), eng.new_status(1)
+    eng.idlma_space_update(Xd.unsqueeze(0), Wd.unsqueeze(0), R.unsqueeze(0), domain=2, eps=float(np.float32(EPS)),
+                           status=status)
+    line(name, "idlma_space_update.W", Wd)
+    line(name, "idlma_space_update.status", status)
+    Wd, status, out = dev(eng, W), eng.new_status(1), dev(eng, raw)
+    for i in range(SHORT):
+        loss, inp = eng.empty((1,), dtype=torch.float64), eng.empty((M, F, T), dtype=torch.float32)
+        eng.idlma_step(Xd, Wd, out, d, ws, domain=domain, dnn_flooring=flooring, eps=EPS, ref=ref, loss=loss,
+                       next_input=inp, status=status)
+        for what, t in (("W", Wd), ("dnn_output", d), ("loss", loss), ("next_input", inp), ("status", status)):
+            line(name, "idlma_step.%d.%s" % (i, what), t)
+        out = inp
+
+
+def factorisations():
     for case in env.MNMF_GRID:
         mnmf(case)
     for case in env.FASTMNMF_GRID:
@@ -327,6 +451,27 @@ def main():
               bool(fx["normalize"]))
     M, T, K, seed = PSDTF_OWN
     psdtf(eng, "own_m%d_t%d_k%d" % (M, T, K), *pt.synthetic(M, T, K, seed), EPS, True)
+
+
+def perbin():
+    eng = Engine(dtype="float64", device="cuda:0")
+    for case in genv.GRID:
+        gradbss(eng, case)
+    for case in penv.GRID:
+        pdsbss(eng, case)
+    for case in benv.GRID:
+        beamform(eng, case)
+    for case in idl.CASES:
+        idlma(eng, case)
+
+
+def main():
+    groups = {"factorisations": factorisations, "perbin": perbin}
+    unknown = [name for name in sys.argv[1:] if name not in groups]
+    if unknown:
+        sys.exit("family_digest.py: unknown group %s; the groups are %s" % (", ".join(unknown), ", ".join(groups)))
+    for name in sys.argv[1:] or groups:
+        groups[name]()
 
 
 if __name__ == "__main__":
